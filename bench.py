@@ -25,6 +25,10 @@ Extra objects in the line:
                   iterations of the same workload on one host core (rank 0, after the timed region, at any N).
   solve_window -- the same K iterations through the reference's own timing window (all of solve(), cg_main.cc:53-55).
 
+--dump-outputs DIR: rank 0 writes what the timed run handed back after its last step (W + K iterations from x0 = 0): the
+solution x (float64, length N) and residual_prev, x_norm and iterations (float64, one element each), as DIR/<name>.npy.
+The inputs depend only on the arguments, so two builds can be compared output for output.
+
 Rank 0 ALWAYS prints a line: if no transport produces a result, if an exception escapes, or if a watchdog expires, the line
 has "value": null and an "error" object.
 """
@@ -91,6 +95,8 @@ def parse_args():
     ap.add_argument("--no-reference-sizes", action="store_true",
                     help="skip the extra `reference_sizes` (one GPU, after the measurement: iterations/s at the reference's own "
                          "sizes N = 1024, 2048 and 4096, the resident persistent kernel beside the per-launch path; ~1 s)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what they computed (x, residual, ||x||, iterations) as DIR/<name>.npy")
     ap.add_argument("--test-hang", default="", help=argparse.SUPPRESS)
     return ap.parse_args()
 
@@ -298,6 +304,24 @@ def reference_sizes(pkg, torch):
     return rows
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, x, res):
+    """--dump-outputs: the arrays a caller of the timed path receives, as out_dir/<name>.npy (float64).  Returns the names."""
+    import numpy as np
+    arrays = {"x": np.ascontiguousarray(x, dtype=np.float64)}
+    for k in ("residual_prev", "x_norm", "iterations"):
+        arrays[k] = np.array([res[k]], dtype=np.float64)
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return sorted(arrays)
+
+
 def problem_size(args, world):
     if args.n:
         return args.n
@@ -343,6 +367,7 @@ class Bench:
         self.gpu_work_s = 0.0          # seconds of solver work this rank put on its GPU (pre-warm, calibration, timed run, window)
         self.gpu_iterations = 0
         self.update_samples = []       # durations (ms) of the event-timed update kernels of the most recent run()
+        self.last_x = None             # the solution x of the most recent run()
         self.rccl_nranks = None        # ncclCommCount of the RCCL candidate (min over ranks), if one was built
 
     # ---- plumbing ------------------------------------------------------------------------------------
@@ -551,6 +576,7 @@ class Bench:
             samples = s.gemv_samples() if self.profile_every else np.zeros(0)
             self.update_samples = s.update_samples() if self.profile_every else np.zeros(0)
             res = s.solve_end(x)
+            self.last_x = x
         except Exception as e:             # noqa: BLE001
             self.log("solve_end failed: %s" % e)
             ok = False
@@ -694,6 +720,10 @@ class Bench:
                 cand.close()
         self.solver = solver
         elapsed, res, samples = out
+        x_out = self.last_x                    # later runs on the solver (solve window, dense leg) replace self.last_x
+        if res["iterations"] != args.warmup + args.steps:
+            raise RuntimeError("the timed run stopped after %d of %d iterations: ms_per_step would not be per step"
+                               % (res["iterations"], args.warmup + args.steps))
         elapsed = self.max_over_ranks(elapsed)
 
         # K1 statistics of every rank: [rows, samples, discarded, min, median, mean, max] (ms)
@@ -725,6 +755,7 @@ class Bench:
 
         if rank != 0:
             return None
+        dumped = dump_outputs(args.dump_outputs, x_out, res) if args.dump_outputs else None
         ms_per_step = elapsed / args.steps * 1e3
         per_rank = []
         for q, (rows_q, cnt, disc, mn, med, avg, mx) in enumerate(k1_rows):
@@ -825,6 +856,8 @@ class Bench:
         if 0 < len(samples) <= 64:
             line["k1_samples_ms"] = [round(float(v), 5) for v in samples]      # rank 0's launches, launch order
         line["residual_after_run"] = res["residual_prev"]
+        if dumped is not None:
+            line["dumped_outputs"] = dumped
         line["iterations_done"] = res["iterations"]
         if window is not None:
             line["solve_window_iterations_per_s"] = window["iterations_per_s"]

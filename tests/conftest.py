@@ -61,6 +61,11 @@ def reference_probe():
 
 
 @pytest.fixture(scope="session")
+def reference_facts():
+    return json.load(open(os.path.join(GOLDEN, "reference_facts.json")))
+
+
+@pytest.fixture(scope="session")
 def oracle_large():
     return json.load(open(os.path.join(GOLDEN, "oracle_large.json")))
 

@@ -2,8 +2,8 @@
 
 The file is the 5-point Laplacian on a 100 x 100 grid (10000 unknowns), lower triangle only,
 `coordinate real symmetric`, 1-based `i j v`, column-major order, 29800 entries
-(/root/reference/code/MPI/lap2D_5pt_n100.mtx:1-3).  tests/test_oracle.py checks that the output is
-byte-identical to the reference's copy whenever /root/reference is present.
+(code/MPI/lap2D_5pt_n100.mtx:1-3 of the reference).  tests/test_oracle.py checks that the output is
+byte-identical to the reference's copy (its sha256 is in reference_facts.json).
 """
 import os
 import sys

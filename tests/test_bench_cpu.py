@@ -123,6 +123,22 @@ def test_traffic_row_must_match_the_plan_that_ran(tmp_path, monkeypatch):
     assert bench.pmc_traffic(32768, 8, None) is None
 
 
+def test_dump_outputs_writes_float64_npy_files(tmp_path):
+    import numpy as np
+    import bench
+    x = np.linspace(-1.0, 1.0, 1000)
+    res = {"residual_prev": 1.5e-3, "x_norm": 12.25, "iterations": 25}
+    names = bench.dump_outputs(str(tmp_path / "out"), x, res)
+    assert names == ["iterations", "residual_prev", "x", "x_norm"]
+    got = {k: np.load(str(tmp_path / "out" / (k + ".npy"))) for k in names}
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["x"], x)
+    assert [got[k][0] for k in ("residual_prev", "x_norm", "iterations")] == [1.5e-3, 12.25, 25.0]
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "big"), np.zeros(bench.DUMP_LIMIT_BYTES // 8 + 1), res)
+    assert not (tmp_path / "big").exists()
+
+
 def test_watchdog_line():
     t0 = time.time()
     r = subprocess.run([sys.executable, BENCH, "--watchdog", "0.05"], capture_output=True, text=True, timeout=120, env=no_gpu_env())

@@ -90,6 +90,29 @@ def test_bench_short_window_statistics(gpu_pkg, oracle):
     assert "update_kernel" not in d          # one GPU: K3 is not event-timed unless asked (--profile-update)
 
 
+def test_bench_dump_outputs(gpu_pkg, oracle, tmp_path):
+    """--dump-outputs: the solution and scalars of the timed run's last step (W + K iterations from x0 = 0) are the oracle's,
+    the line's, and the same in a second run with the same arguments."""
+    import numpy as np
+    n, warmup, steps = 4096, 5, 20
+    outs = []
+    for run in ("a", "b"):
+        r = subprocess.run([sys.executable, BENCH, "--steps", str(steps), "--warmup", str(warmup), "--matrix-size", str(n),
+                            "--no-cpu-baseline", "--no-live-pmc", "--no-solve-window", "--no-reference-sizes",
+                            "--dump-outputs", str(tmp_path / run)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = one_line(r.stdout)
+        assert d["dumped_outputs"] == ["iterations", "residual_prev", "x", "x_norm"]
+        got = {k: np.load(str(tmp_path / run / (k + ".npy"))) for k in d["dumped_outputs"]}
+        assert all(a.dtype == np.float64 for a in got.values()) and got["x"].shape == (n,)
+        assert got["iterations"][0] == d["iterations_done"] == warmup + steps and got["residual_prev"][0] == d["residual_after_run"]
+        outs.append(got)
+    xo, ro = oracle.solve_lap2d(n, warmup + steps, 0.0, 1)
+    assert np.linalg.norm(outs[0]["x"] - xo) / np.linalg.norm(xo) < 1e-12
+    assert abs(outs[0]["residual_prev"][0] - ro["residual_prev"]) <= 1e-6 * ro["residual_prev"]
+    assert np.allclose(outs[0]["x"], outs[1]["x"], rtol=1e-13, atol=0.0)
+
+
 def test_bench_rccl_one_rank_under_the_launcher(gpu_pkg, oracle):
     """--transport rccl with one rank under torch.distributed.run: ncclGetUniqueId, the broadcast of the id,
     ncclCommInitRank, one ncclAllGather per iteration on the library's stream, ncclCommCount in the line.  RCCL refuses

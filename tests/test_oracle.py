@@ -1,6 +1,7 @@
 """CPU tests of the parity oracle (oracle/cg_oracle.c) against the reference outputs recorded by the
 survey (tests/golden/reference_probe.json) and against structural truths of the reference's code.
 These pin the oracle; the GPU tests then compare libcgx with the oracle."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -193,11 +194,14 @@ def test_config2_oracle_run_to_convergence_is_pinned(reference_probe, oracle_lar
 
 
 # ---- Matrix-Market input surface -----------------------------------------------------------------------
-def test_mtx_fixture_is_the_reference_file(mtx_path):
+def test_mtx_fixture_is_the_reference_file(mtx_path, reference_facts):
+    """Byte for byte the reference's file: its size and sha256 are recorded in tests/golden/reference_facts.json."""
+    data = open(mtx_path, "rb").read()
+    want = reference_facts["lap2D_5pt_n100.mtx"]
+    assert len(data) == want["bytes"] and hashlib.sha256(data).hexdigest() == want["sha256"]
     ref = os.path.join(REF, "lap2D_5pt_n100.mtx")
-    if not os.path.exists(ref):
-        pytest.skip("reference tree not present on this machine")
-    assert open(mtx_path, "rb").read() == open(ref, "rb").read()
+    if os.path.exists(ref):
+        assert data == open(ref, "rb").read()
 
 
 def test_mtx_reader(oracle, mtx_path):
@@ -233,16 +237,23 @@ MTX_CASES = {
 }
 
 
-def test_oracle_reader_matches_the_reference_reader(oracle, mtx_path, tmp_path):
-    if not oracle.ref_available():
-        pytest.skip("oracle/_ref not built (needs /root/reference: `make -C oracle ref`)")
-    A_ref = oracle.ref_read_mtx_dense(mtx_path)
+def test_oracle_reader_matches_the_reference_reader(oracle, mtx_path, tmp_path, reference_facts):
+    """Against what the reference's reader made of each file (tests/golden/reference_facts.json), and against the reader
+    itself where oracle/_ref was built."""
+    got = reference_facts["ref_reader"]
     A, _, _ = oracle.read_mtx_dense(mtx_path)
-    assert np.array_equal(A, A_ref)
+    want = got["lap2D_5pt_n100.mtx"]
+    assert list(A.shape) == want["shape"] and np.count_nonzero(A) == want["nnz"]
+    assert hashlib.sha256(np.ascontiguousarray(A, dtype=np.float64).tobytes()).hexdigest() == want["sha256"]
+    if oracle.ref_available():
+        assert np.array_equal(A, oracle.ref_read_mtx_dense(mtx_path))
     for name, text in MTX_CASES.items():
         f = tmp_path / name
         f.write_text(text)
-        assert np.array_equal(oracle.read_mtx_dense(str(f))[0], oracle.ref_read_mtx_dense(str(f))), name
+        B = oracle.read_mtx_dense(str(f))[0]
+        assert np.array_equal(B, np.array(got[name]["dense"], dtype=np.float64)), name
+        if oracle.ref_available():
+            assert np.array_equal(B, oracle.ref_read_mtx_dense(str(f))), name
 
 
 # ---- the on-the-fly twin used as checker for libcgx's opt-in banded storage at large n -------------------------

@@ -1,18 +1,17 @@
 """the files experiments/cg_mi355x.run leaves under results/ must go through the loaders of the
 reference's plots.ipynb.  The loaders are restated here in a few lines each (what they do to a line, which tables they
-index), citing the notebook's source lines (numbering of its first code cell); where the notebook itself is present
-(/root/reference, this container only) its ALPHAS table is read from it and compared with the restatement."""
+index), citing the notebook's source lines (numbering of its first code cell); the notebook's ALPHAS table, ITEMS and BETAS
+slice, recorded in tests/golden/reference_facts.json (tests/golden/make_reference_facts.py), are compared with the restatement."""
 import json
 import math
 import os
-import re
 
 import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 RES = os.path.join(ROOT, "results")
-NOTEBOOK = "/root/reference/plots.ipynb"
+FACTS = os.path.join(ROOT, "tests", "golden", "reference_facts.json")
 
 # plots.ipynb:5-6 -- serial fractions per matrix size; show_hard_MPI_results indexes it with every n of the file
 ALPHA_KEYS = [1024, 1148, 2048, 2896, 4096, 5792, 8192, 11585, 16384]
@@ -56,12 +55,9 @@ def no_blank_or_ragged_lines(path):
 
 
 def test_alphas_table_is_the_notebooks():
-    if not os.path.exists(NOTEBOOK):
-        pytest.skip("reference notebook not present on this machine")
-    src = "".join("".join(c["source"]) for c in json.load(open(NOTEBOOK))["cells"] if c["cell_type"] == "code")
-    table = re.search(r"ALPHAS\s*=\s*\{(.*?)\}", src, re.S).group(1)
-    assert [int(k) for k in re.findall(r"(\d+)\s*:", table)] == ALPHA_KEYS
-    assert "ITEMS = 7" in src and "list(ALPHAS.values())[2:]" in src
+    nb = json.load(open(FACTS))["plots_ipynb"]
+    assert [k for k, _ in nb["alphas"]] == ALPHA_KEYS
+    assert nb["items"] == 7 and nb["betas_slice_start"] == 2
 
 
 @pytest.mark.parametrize("name", ["strong_scaling.txt", "strong_scaling_n32768.txt"])
@@ -118,6 +114,7 @@ def test_plot_script_reads_every_committed_file_without_an_edit(tmp_path):
     pm = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(pm)
     assert list(pm.ALPHAS) == ALPHA_KEYS
+    assert [[k, v] for k, v in pm.ALPHAS.items()] == json.load(open(FACTS))["plots_ipynb"]["alphas"]
     for name in ("strong_scaling.txt", "strong_scaling_n32768.txt"):
         mine, ref = pm.strong_series(os.path.join(RES, name)), load_strong(os.path.join(RES, name))
         assert list(mine) == list(ref)
