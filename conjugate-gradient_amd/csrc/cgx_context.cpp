@@ -89,6 +89,7 @@ void free_shard(Shard &s)
     (void)hipFree(s.partials);
     (void)hipFree(s.ap_parts);
     (void)hipFree(s.k1_scratch);
+    (void)hipFree(s.sym_parts);
     (void)hipFree(s.sc);
     (void)hipFree(s.gathered);
     s = Shard{};
@@ -421,6 +422,54 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
         HIP_TRY(ctx, hipMemcpy(ctx->d_scalar_ptrs, sp.data(), nlocal * sizeof(Scalars *), hipMemcpyHostToDevice));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return CGX_OK;
+}
+
+cgx_status plan_symmetric(cgx_ctx *ctx)
+{
+    if (ctx->shards.size() != 1 || ctx->nranks != 1 || ctx->banded || ctx->chunked) return CGX_OK;
+    Shard &s = ctx->shards[0];
+    int variant = ctx->cfg.gemv_variant;
+    if (variant <= 0) {
+        const char *e = getenv("CGX_GEMV_VARIANT");
+        if (e) variant = atoi(e);
+    }
+    // the general K1 exactly as setup_problem plans it for this shard (an explicit shape, 10821 say, stays what it asks for)
+    const int k1_variant = (variant == 40000 || variant == 50000) ? 0 : variant;
+    const cgx::GemvPlan general = cgx::plan_gemv(k1_variant, s.rows, ctx->n, ctx->lda, false);
+    const cgx::GemvPlan sym = cgx::plan_symv(ctx->n, ctx->lda, ctx->cus);
+    const bool eligible = variant <= 0 && ctx->n > cgx::kSymvMinN && s.rows == ctx->n && s.A && sym.light <= ctx->npart;
+    if (!eligible) {
+        s.plan = general;
+        return CGX_OK;
+    }
+    // one read of A per problem set-up; the host waits for the flag once
+    DeviceScratch scratch;
+    int *dflag = nullptr;
+    HIP_TRY(ctx, scratch.alloc(&dflag, sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(dflag, 0, sizeof(int), ctx->stream));
+    HIP_TRY(ctx, cgx::launch_symmetric_check(s.A, ctx->lda, ctx->n, dflag, ctx->stream));
+    int mismatch = 1;
+    HIP_TRY(ctx, hipMemcpyAsync(&mismatch, dflag, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (mismatch) {
+        s.plan = general;
+        return CGX_OK;
+    }
+    const size_t bytes = (size_t)sym.split * (size_t)ctx->lda * sizeof(double);
+    if (s.sym_parts && s.sym_parts_bytes != bytes) {
+        (void)hipFree(s.sym_parts);
+        s.sym_parts = nullptr;
+        s.sym_parts_bytes = 0;
+    }
+    if (!s.sym_parts) {
+        // zeroed once: rows from n on are never written and the fold adds them up for the pair (n-1, n) of an odd n
+        HIP_TRY(ctx, hipMalloc(&s.sym_parts, bytes));
+        s.sym_parts_bytes = bytes;
+        HIP_TRY(ctx, hipMemsetAsync(s.sym_parts, 0, bytes, ctx->stream));
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    }
+    s.plan = sym;
     return CGX_OK;
 }
 

@@ -1,8 +1,11 @@
-// cgx_device.h -- device-side helpers shared by the kernel translation units (cgx_kernels.hip, cgx_resident.hip):
-// the fixed-order reductions, the safeguard of alpha, and the tagged-word store.  Device code only.
+// cgx_device.h -- device-side helpers shared by the kernel translation units (cgx_kernels.hip, cgx_symv.hip, cgx_resident.hip):
+// the fixed-order reductions, the safeguard of alpha, the tagged-word store, and the iteration head of the per-launch
+// GEMV kernels.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
+
+#include "cgx_kernels.h"
 
 namespace cgx {
 
@@ -114,6 +117,140 @@ __device__ __forceinline__ void tagged_store(unsigned long long *dst, double v, 
     const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
     const u4 w = {(unsigned)bits, tag, (unsigned)(bits >> 32), tag};   // little endian: {lo32 | tag<<32}, {hi32 | tag<<32}
     asm volatile("global_store_dwordx4 %0, %1, off sc0 sc1" : : "v"(dst), "v"(w) : "memory");
+}
+
+
+// ------------------------------------------------------------------------------------------------
+// shared by the per-launch GEMV kernels (cgx_kernels.hip: K1; cgx_symv.hip: the symmetric form)
+// ------------------------------------------------------------------------------------------------
+template <bool NT>
+__device__ __forceinline__ d2 load_a(const double *ptr)
+{
+    if constexpr (NT) return __builtin_nontemporal_load(reinterpret_cast<const d2 *>(ptr));
+    else return *reinterpret_cast<const d2 *>(ptr);
+}
+
+// ------------------------------------------------------------------------------------------------
+// the exchanged residual (SegView) and the scalar sums over ranks
+// ------------------------------------------------------------------------------------------------
+// Owner of column c: q = min(c / n_loc, nranks-1), without an integer division: the host supplies the
+// round-up magic number (div_magic, div_shift) for n_loc (seg_finalize), exact for 0 <= c < 2^31.
+__device__ __forceinline__ int seg_owner(const SegView &sv, int c)
+{
+    if (sv.n_loc <= 0) return sv.nranks - 1;   // N < P: floor(N/P) = 0 rows everywhere but on the last rank (cg.cc:255-266)
+    const int t = (sv.div_shift == 32) ? c : (int)(__umulhi((unsigned)c, sv.div_magic) >> sv.div_shift);
+    return t < sv.nranks - 1 ? t : sv.nranks - 1;
+}
+
+__device__ __forceinline__ double seg_load(const SegView &sv, int c)   // r[c], c < n
+{
+    const int q = (sv.nranks > 1) ? seg_owner(sv, c) : 0;
+    return sv.base[c + q * sv.seg_gap];   // q*S + (c - q*n_loc)
+}
+
+__device__ __forceinline__ double seg_sum_slot(const SegView &sv, int slot)
+{
+    double s = sv.base[sv.Sr + slot];
+    for (int q = 1; q < sv.nranks; ++q) s += sv.base[(long)q * sv.S + sv.Sr + slot];   // rank order
+    return s;
+}
+
+// gathered layout on every shard: [rank q][slot v], kSlots doubles per rank
+__device__ __forceinline__ double sum_ranks(const double *__restrict__ gathered, int slot, int nranks)
+{
+    double s = gathered[slot];
+    for (int q = 1; q < nranks; ++q) s += gathered[q * kSlots + slot];   // rank order, same on every shard
+    return s;
+}
+
+// Tail of iteration k-1, evaluated redundantly (and identically) by every WAVE of K1(k).
+// r.r = fixed-order fold of K3's per-workgroup partials (the tail of the replicated-r segment): every wave of every
+// workgroup of every rank folds the same values the same way (lane-strided sums, then the shuffle butterfly), so the
+// break decision is the same everywhere, and no in-kernel grid reduction (ticket + fences, ~4 us at the end of K3) is
+// needed.  No LDS and no workgroup barrier: on gfx9 a barrier's release fence drains vmcnt, i.e. it would wait for every
+// A load a kernel has already issued ahead of the head.  The head is cut in two so that a kernel can put its first
+// A loads between the halves: head_issue sends out the head's own loads (done, rsold, up to 256 partials), head_finish
+// consumes them -- loads return in order, so the wait in between covers the head's loads only.
+struct IterHead {
+    double beta;
+    bool stop;
+};
+
+struct HeadLoads {
+    double rsold;
+    int done;
+    double a[4];
+};
+
+__device__ __forceinline__ HeadLoads head_issue(const Scalars *sc, const SegView &sv, int k)
+{
+    HeadLoads hl;
+    const int nparts = sv.S - sv.Sr, lane = threadIdx.x & 63;
+    const double *part = sv.base + sv.Sr;
+    hl.done = sc->done;                                  // converged earlier: the whole grid drains immediately
+    hl.rsold = sc->rs[(k > 0 ? k - 1 : 0) & 1];          // stored by the previous K1: independent of the fold
+    // unconditional loads (clamped index, value discarded by a select): a load behind a branch would make the number of
+    // loads in flight path dependent, and the compiler then waits for ALL of them (vmcnt(0)) instead of counting
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int t = lane + 64 * u;
+        const double val = part[t < nparts ? t : nparts - 1];
+        hl.a[u] = (t < nparts) ? val : 0.0;
+    }
+    return hl;
+}
+
+__device__ __forceinline__ IterHead head_finish(const HeadLoads &hl, Scalars *sc, const SegView &sv, int k, double tol)
+{
+    IterHead h{0.0, false};
+    const int nparts = sv.S - sv.Sr, lane = threadIdx.x & 63;
+    const double *part = sv.base + sv.Sr;
+    double v = (hl.a[0] + hl.a[1]) + (hl.a[2] + hl.a[3]);
+    for (int t = lane + 256; t < nparts; t += 256) {     // more than 256 partials: n > 65536
+        const double a0 = part[t], a1 = (t + 64 < nparts) ? part[t + 64] : 0.0;
+        const double a2 = (t + 128 < nparts) ? part[t + 128] : 0.0, a3 = (t + 192 < nparts) ? part[t + 192] : 0.0;
+        v += (a0 + a1) + (a2 + a3);
+    }
+    const double rsnew = wave_sum(v);                                // r.r over all rows, cg.cc:116-117 (k==0: cg.cc:91-92)
+    const bool first = (blockIdx.x == 0 && threadIdx.x == 0) && !hl.done;   // nothing is written once converged
+    if (k == 0) {                                                    // p = r (cg.cc:85): beta = 0, p_old = 0
+        if (first) { sc->rs[0] = rsnew; sc->rs[1] = rsnew; }
+        return h;
+    }
+    if (first) sc->rs[k & 1] = rsnew;                                // rsold = rsnew, cg.cc:132
+    if (sqrt(rsnew) < tol) {                                         // cg.cc:120-121: break before the p update
+        if (first) { sc->k_final = k - 1; sc->done = 1; }
+        h.stop = true;
+        return h;
+    }
+    h.beta = rsnew / hl.rsold;                                       // cg.cc:124
+    return h;
+}
+
+// Both halves back to back; *done = the flag as loaded.  All lanes of the wave must be active (shuffles).
+__device__ __forceinline__ IterHead iteration_head(Scalars *sc, const SegView &sv, int k, double tol, int *done)
+{
+    const HeadLoads hl = head_issue(sc, sv, k);
+    *done = hl.done;
+    return head_finish(hl, sc, sv, k, tol);
+}
+
+// p_new for the column pair (c, c+1); pad columns (>= n) stay exactly 0.
+// SINGLE (one shard): r is contiguous and zero padded up to lda, one 16-B load.
+template <bool SINGLE>
+__device__ __forceinline__ d2 make_p(const SegView &sv, double beta, d2 p_old, int c)
+{
+    d2 r;
+    if constexpr (SINGLE) {
+        r = *reinterpret_cast<const d2 *>(sv.base + c);
+    } else {
+        r.x = (c < sv.n) ? seg_load(sv, c) : 0.0;
+        r.y = (c + 1 < sv.n) ? seg_load(sv, c + 1) : 0.0;
+    }
+    d2 p;
+    p.x = fma(beta, p_old.x, r.x);                                   // cg.cc:127-129
+    p.y = fma(beta, p_old.y, r.y);
+    return p;
 }
 
 }  // namespace cgx

@@ -38,6 +38,8 @@ struct Shard {
     double *k1_scratch = nullptr;   // chunked exchange: where K1's per-workgroup p.Ap partials go (only the gemv probe reads them;
                                     // the segment tail then holds one partial per chunk of the slice instead)
     double *partials = nullptr;  // scratch: per-workgroup partial sums of K3 and of the setup kernels
+    double *sym_parts = nullptr; // plan variant 6 (exactly symmetric A, cgx_symv.hip): nb x lda doubles, the tile kernel's slots
+    size_t sym_parts_bytes = 0;
     Scalars *sc = nullptr;
     double *gathered = nullptr;  // kMaxRanks * kSlots doubles (DEBUG scalars of all ranks)
     cgx::GemvPlan plan{};
@@ -241,6 +243,9 @@ void free_problem(cgx_ctx *ctx);
 void bind_state(cgxi::Shard &s, long lda);     // point x / rbuf / p[1] / sc (and rv.base) into state[cur]
 long p2p_fixed_prefix(int nranks);
 cgx_status setup_problem(cgx_ctx *ctx, int n);       // allocate the shards of an n x n problem (contents: caller)
+// Behind every writer of A: where the symmetric K1 could run (one shard, dense, n > kSymvMinN, the default plan) A is checked for
+// exact symmetry on the device, and the plan becomes variant 6 or the general K1 accordingly (both ways).
+cgx_status plan_symmetric(cgx_ctx *ctx);
 
 // cgx_matrix.cpp
 cgx_status alloc_dia(cgx_ctx *ctx, Shard &s, const std::vector<int> &offs);

@@ -81,6 +81,28 @@ hipError_t launch_gemv_fused(const GemvPlan &plan, const double *A, long lda, in
                              const double *p_old, double *p_new, SegView seg, double *Ap, double *partials,
                              Scalars *sc, int k, double tol, hipStream_t s, hipEvent_t e_start = nullptr,
                              hipEvent_t e_stop = nullptr, long ap_stride = 0);
+// ---- K1 for an exactly symmetric A on one GPU (plan variant 6, cgx_symv.hip) ----------------------------------------------
+// A p from the upper triangle's B x B tiles: each off-diagonal tile is read once and used twice.  The plan's fields mean:
+// R = tile edge B, U = tiles of the longest workgroup run, waves = 4, light = fold workgroups (= p.Ap partials in the tail),
+// split = nb (blocks of B rows = slots per row of the partial buffer, nb x lda doubles, zeroed when made), grid = workgroups of
+// the tile kernel, ncols as for variant 1.
+constexpr int kSymvTile = 256;
+constexpr int kSymvMinN = 16384;   // the default plan takes variant 6 only above this n
+GemvPlan plan_symv(int n, long lda, int cus);
+// p.Ap partials a plan's launch leaves in the tail (variant 6: one per fold workgroup; otherwise one per K1 workgroup)
+inline int plan_partials(const GemvPlan &pl) { return pl.variant == 6 ? pl.light : pl.grid / (pl.split > 1 ? pl.split : 1); }
+// Plain form: Ap = A v (rows < n), partials[wg] = the fold workgroup's part of v . Ap.
+hipError_t launch_symv_plain(const GemvPlan &pl, const double *A, long lda, int n, const double *v, double *parts, double *Ap,
+                             double *partials, hipStream_t s);
+// Fused form: the contract of launch_gemv_fused on one shard (iteration head, p_new = r + beta p_old stored once, Ap, one p.Ap
+// partial per fold workgroup, nothing stored once converged).  Two dispatches: e_start is bound to the tile kernel's, e_stop to
+// the fold's, so the pair spans all the work that produces Ap.
+hipError_t launch_symv_fused(const GemvPlan &pl, const double *A, long lda, int n, const double *p_old, double *p_new, SegView seg,
+                             double *parts, double *Ap, double *partials, Scalars *sc, int k, double tol, hipStream_t s,
+                             hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr);
+// *mismatch |= 1 unless A (n x n at pitch lda) equals its transpose bit for bit (64-bit words; *mismatch zeroed by the caller).
+hipError_t launch_symmetric_check(const double *A, long lda, int n, int *mismatch, hipStream_t s);
+
 // Chunks of a rank's Ap slice (see "Chunks" in cgx_kernels.hip): kChunkRows consecutive rows, one workgroup each.
 constexpr int kChunkRows = 512;
 inline int chunks_per_rank(int Sr) { return (Sr + kChunkRows - 1) / kChunkRows; }

@@ -83,6 +83,7 @@ cgx_status cgx_generate_lap2d_matrix(cgx_ctx *ctx, int size)
             HIP_TRY(ctx, cgx::launch_generate_lap2d(s.A, ctx->lda, size, s.row0, s.rows, ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CGX_TRY(plan_symmetric(ctx));
     ctx->have_matrix = true;
     return CGX_OK;
 }
@@ -130,6 +131,7 @@ cgx_status cgx_set_matrix_dense(cgx_ctx *ctx, const double *A, long lda_host, in
         HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CGX_TRY(plan_symmetric(ctx));
     ctx->have_matrix = true;
     return CGX_OK;
 }
@@ -413,6 +415,7 @@ cgx_status cgx_read_matrix(cgx_ctx *ctx, const char *path)
                                             static_cast<unsigned char *>(dwin.p), ctx->stream));
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    CGX_TRY(plan_symmetric(ctx));
     ctx->have_matrix = true;
     return CGX_OK;
 }

@@ -32,7 +32,7 @@ cgx_status cgx_probe_gemv(cgx_ctx *ctx, const double *p, double *y, double *pAp)
         HIP_TRY(ctx, hipMemsetAsync(s.sc, 0, sizeof(Scalars), st));
         HIP_TRY(ctx, hipMemcpyAsync(s.p[0], p, (size_t)ctx->n * sizeof(double), hipMemcpyHostToDevice, st));
         CGX_TRY(run_gemv_plain(ctx, s, s.p[0]));
-        HIP_TRY(ctx, cgx::launch_reduce_partials(s.k1_part(), s.plan.grid / std::max(s.plan.split, 1), &s.sc->local[cgx::kSlotConj], st));
+        HIP_TRY(ctx, cgx::launch_reduce_partials(s.k1_part(), cgx::plan_partials(s.plan), &s.sc->local[cgx::kSlotConj], st));
         double part = 0.0;
         if (s.rows > 0)
             HIP_TRY(ctx, hipMemcpyAsync(y + s.row0, s.Ap(), (size_t)s.rows * sizeof(double), hipMemcpyDeviceToHost, st));
@@ -333,7 +333,7 @@ cgx_status cgx_probe_fill_matrix_hash(cgx_ctx *ctx, unsigned long long seed, int
     for (auto &s : ctx->shards)
         HIP_TRY(ctx, cgx::launch_fill_hash(s.A, ctx->lda, ctx->n, s.row0, s.rows, seed, symmetric ? 1 : 0, diag, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return CGX_OK;
+    return plan_symmetric(ctx);   // the plan follows the new contents (variant 6 only for an exactly symmetric block)
 }
 
 cgx_status cgx_probe_get_matrix_rows(cgx_ctx *ctx, int local_shard, double *A_out, int *row0, int *rows)

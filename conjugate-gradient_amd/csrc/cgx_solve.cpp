@@ -144,6 +144,8 @@ cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full)
     if (ctx->banded)
         HIP_TRY(ctx, cgx::launch_spmv_dia_plain(s.plan, s.dia, s.rows, s.row0, ctx->n, ctx->lda, v_full, s.Ap(), s.k1_part(), s.sc,
                                                 ctx->stream));
+    else if (s.plan.variant == 6)   // exactly symmetric A, one shard (cgx_symv.hip)
+        HIP_TRY(ctx, cgx::launch_symv_plain(s.plan, s.A, ctx->lda, ctx->n, v_full, s.sym_parts, s.Ap(), s.k1_part(), ctx->stream));
     else
         HIP_TRY(ctx, cgx::launch_gemv_plain(s.plan, s.A, ctx->lda, s.rows, v_full, v_full + s.row0, s.Ap(), s.k1_part(),
                                             s.sc, ctx->stream));
@@ -183,6 +185,9 @@ cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
     if (ctx->banded)
         HIP_TRY(ctx, cgx::launch_spmv_dia_fused(s.plan, s.dia, s.rows, s.row0, ctx->n, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1],
                                                 s.rv, s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1));
+    else if (s.plan.variant == 6)   // the event pair spans the tile kernel and the fold: all the work that produces Ap
+        HIP_TRY(ctx, cgx::launch_symv_fused(s.plan, s.A, ctx->lda, ctx->n, s.p[k & 1], s.p[(k + 1) & 1], s.rv, s.sym_parts, s.Ap(),
+                                            s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1));
     else
         HIP_TRY(ctx, cgx::launch_gemv_fused(s.plan, s.A, ctx->lda, s.rows, s.row0, s.p[k & 1], s.p[(k + 1) & 1], s.rv,
                                             s.plan.split > 1 ? s.ap_parts : s.Ap(),
@@ -263,8 +268,10 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
     for (auto &s : ctx->shards) {
         hipEvent_t u0 = nullptr, u1 = nullptr;
         if (&s == &ctx->shards[0]) CGX_TRY(take_update_events(ctx, &u0, &u1));
+        // (variant 6: the fold's partials, fewer than the tail holds)
+        const int count = folded ? 1 : (s.plan.variant == 6 ? cgx::plan_partials(s.plan) : ctx->npart);
         HIP_TRY(ctx, cgx::launch_update_xr(ctx->n, s.rows, s.row0, s.p[(k + 1) & 1], s.apv, folded ? ctx->npart : 0,
-                                           folded ? 1 : ctx->npart, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1));   // cg.cc:105-116
+                                           count, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1));   // cg.cc:105-116
     }
     return CGX_OK;
 }

@@ -171,11 +171,15 @@ cgx_status  cgx_get_comm_info(cgx_ctx *ctx, int *comm_mode, int *ranks_wired, in
 
 /* The K1 (GEMV, cg.cc:100-102) launch shape the library planned for local shard `local_shard` of the current problem,
  * for the benchmark record (which kernel ran): out = {variant (1 column-split, 2 LDS-staged p tiles, 3 banded, 4 = the loop
- * runs in the resident persistent kernel, 5 = in the streaming persistent kernel), R rows per workgroup (variant 2: per
+ * runs in the resident persistent kernel, 5 = in the streaming persistent kernel, 6 = symmetric A from its upper triangle), R rows per workgroup (variant 2: per
  * wave), U steps in flight (variant 4 / 5: column steps of 512 / 1024), waves per workgroup, light (1 = the one-round form;
  * variant 4: rows of a workgroup held in registers, 0 up to n = 2048; variant 5: rows per batch of the ring), split (column
  * pieces per row group, tied to the XCDs; variant 5: rows of a workgroup that stay in LDS and registers instead of being streamed), grid (workgroups of one fused launch; variant 4 / 5: of the persistent kernel, all
- * resident at once), ncols (columns swept)}.  After a persistent launch has been redone on the per-launch path (gemv_variant
+ * resident at once), ncols (columns swept)}.
+ * Variant 6 = one GPU, dense, n > 16384, the default plan and an A that equals its transpose bit for bit (checked on the device
+ * behind every writer of A): A p from the upper triangle's B x B tiles (csrc/cgx_symv.hip); then R = B, U = tiles of the longest
+ * workgroup run, waves = 4, light = workgroups of the fold kernel (= p.Ap partials), split = nb = ceil(n / B) (slots per row of
+ * the partial buffer), grid = workgroups of the tile kernel, ncols as for variant 1.  After a persistent launch has been redone on the per-launch path (gemv_variant
  * above) this reports the per-launch shape. */
 #define CGX_GEMV_PLAN_INTS 8
 cgx_status  cgx_get_gemv_plan(const cgx_ctx *ctx, int local_shard, int out[CGX_GEMV_PLAN_INTS]);
