@@ -131,6 +131,33 @@ def hash_rows_numpy(n, rows, seed, symmetric=False, diag=0.0):
     return A
 
 
+def hash_gemv_longdouble(n, seed, p, symmetric=False, diag=0.0, ranges=None, chunk=1024):
+    """y = A p for the hash matrix (hash_rows) with every row summed in np.longdouble (x87 extended: a 64-bit mantissa), and
+    |A| |p| in double for the error bound.  ranges: list of (row0, nrows) (default: all rows), rebuilt `chunk` rows at a time so
+    host memory stays bounded.  Returns (rows, y, abs_ap): the row indices in order, y as longdouble, abs_ap as float64.
+    p . (A p) near-exactly, where rows cover the matrix: np.sum(p[rows].astype(np.longdouble) * y)."""
+    assert np.finfo(np.longdouble).nmant >= 63, "np.longdouble has no 64-bit mantissa on this host"
+    p = np.ascontiguousarray(p, dtype=np.float64)
+    pl = p.astype(np.longdouble)
+    pa = np.abs(p)
+    rows, ys, bs = [], [], []
+    for r0, cnt in ([(0, n)] if ranges is None else ranges):
+        for c0 in range(r0, r0 + cnt, chunk):
+            c = min(chunk, r0 + cnt - c0)
+            A = hash_rows(n, c0, c, seed, symmetric, diag)
+            ys.append(A.astype(np.longdouble) @ pl)
+            bs.append(np.abs(A) @ pa)
+            rows.append(np.arange(c0, c0 + c))
+    return np.concatenate(rows), np.concatenate(ys), np.concatenate(bs)
+
+
+def gemv_rows_outside(y, y_ref, abs_ap, n):
+    """Positions where y (float64) differs from the near-exact y_ref by more than the suite's summation-order bound
+    4e-16 sqrt(n) (|A| |p|)_i: any order of n double products and sums stays inside it."""
+    err = np.abs(np.asarray(y, dtype=np.longdouble) - y_ref)
+    return np.nonzero(err > 4e-16 * np.sqrt(n) * abs_ap)[0]
+
+
 def init_source_term(n, h=None):
     b = np.empty(n, dtype=np.float64)
     lib().oracle_init_source_term(n, (1.0 / n) if h is None else h, _dp(b))

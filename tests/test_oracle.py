@@ -369,6 +369,40 @@ def test_hash_matrix_with_dominant_diagonal_is_spd(oracle):
     assert r["converged"] and r["rel_residual"] < 1e-11
 
 
+def test_longdouble_hash_gemv_and_its_row_check(oracle):
+    """The reference product of tests/test_gpu_symmetric_parity.py: at small n it agrees with oracle.gemv, its chunked row
+    ranges are the same numbers, and its row check sees the faults a tiled symmetric product could have -- one tile's row
+    piece A_IJ p_J or column piece A_IJ^T p_I missing from one wave's 64 rows, one slot of a row counted twice."""
+    n, seed, B = 700, 0x5EED, 256   # three 256-row blocks, the last one partial
+    p = np.random.default_rng(7).standard_normal(n)
+    A = oracle.hash_rows(n, 0, n, seed, True, 0.0)
+    rows, y, abs_ap = oracle.hash_gemv_longdouble(n, seed, p, symmetric=True, chunk=128)
+    assert y.dtype == np.longdouble and np.array_equal(rows, np.arange(n))
+    assert np.allclose(abs_ap, np.abs(A) @ np.abs(p), rtol=1e-13, atol=0.0)
+    yo = oracle.gemv(A, p)
+    assert oracle.gemv_rows_outside(yo, y, abs_ap, n).size == 0
+    pap = np.sum(p.astype(np.longdouble) * y)
+    assert abs(float(pap) - oracle.dot(p, yo)) <= float(np.sum(np.abs(p) * 4e-16 * np.sqrt(n) * abs_ap))
+    r2, y2, b2 = oracle.hash_gemv_longdouble(n, seed, p, symmetric=True, ranges=[(300, 70), (0, 5)], chunk=32)
+    assert np.array_equal(r2, np.r_[300:370, 0:5]) and np.array_equal(y2, y[r2]) and np.allclose(b2, abs_ap[r2], rtol=1e-13, atol=0.0)
+
+    def outside(ybad):
+        return set(oracle.gemv_rows_outside(ybad, y, abs_ap, n).tolist())
+
+    w1, J = slice(64, 128), slice(2 * B, n)            # row piece of tile (0, 2) missing from wave 1 of block 0
+    ybad = yo.copy()
+    ybad[w1] -= A[w1, J] @ p[J]
+    assert outside(ybad) == set(range(64, 128))
+    w2, I = slice(2 * B + 128, n), slice(0, B)         # column piece of tile (0, 2) missing from wave 2 of block 2 (60 rows)
+    ybad = yo.copy()
+    ybad[w2] -= A[I, w2].T @ p[I]
+    assert outside(ybad) == set(range(2 * B + 128, n))
+    blk1 = slice(B, 2 * B)                             # slot 0 of block 1 (tile (0, 1), column piece) added twice
+    ybad = yo.copy()
+    ybad[blk1] += A[I, blk1].T @ p[I]
+    assert outside(ybad) == set(range(B, 2 * B))
+
+
 # ---- the third-party arithmetic: the same recurrence through a real OpenBLAS -----------------------------------------------
 def _solve_through_openblas(A, b, max_iter, tol, psize=1):
     """code/MPI/cg.cc:38-156 once more, with the three BLAS calls of the reference (cblas_dgemv cg.cc:80,101,146; cblas_ddot
