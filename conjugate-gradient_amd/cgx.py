@@ -32,7 +32,9 @@ EXPORTS = [
     "cgx_probe_get_source_term", "cgx_probe_set_fault_after", "cgx_probe_set_resident_limit", "cgx_probe_persistent_plan",
     "cgx_probe_parse_matrix_market", "cgx_probe_p2p_mailbox_to_host", "cgx_probe_fill_matrix_hash",
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
+    "cgx_solve_multi", "cgx_probe_gemv_multi",
 ]
+MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 
 
 class Config(C.Structure):
@@ -140,6 +142,8 @@ def lib():
         L.cgx_probe_set_p2p_epoch.argtypes = [vp, C.c_int, C.c_ulonglong]
         L.cgx_probe_resident_test.argtypes = [vp, C.c_ulonglong, C.c_int]
         L.cgx_probe_get_p2p_epoch.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
+        L.cgx_solve_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_probe_gemv_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, dp]
         L.cgx_probe_parse_matrix_market.argtypes = [C.c_char_p, C.c_int, ip, ip, ip, ip, ip, ip, dp, C.c_long, C.c_char_p, C.c_int]
         for name in EXPORTS:
             fn = getattr(L, name)
@@ -342,6 +346,28 @@ class CGSolver:
         res = Result()
         self._check(lib().cgx_solve(self._h, _dp(x), C.byref(res)))
         return res.as_dict()
+
+    def solve_multi(self, B, X=None):
+        """B: float64 array (k, n), one right-hand side per row; X: initial guesses of the same shape (None = zeros).
+        Returns (X, [k result dicts]): k independent CG solves on the current matrix, one pass over A per iteration."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[1] == self.n(), B.shape
+        X = np.zeros_like(B) if X is None else np.array(X, dtype=np.float64, copy=True, order="C")
+        assert X.shape == B.shape, (X.shape, B.shape)
+        k = B.shape[0]
+        res = (Result * max(k, 1))()
+        self._check(lib().cgx_solve_multi(self._h, int(k), _dp(B), int(B.shape[1]), _dp(X), int(X.shape[1]), res))
+        return X, [res[j].as_dict() for j in range(k)]
+
+    def probe_gemv_multi(self, P):
+        """P: float64 array (k, n).  Returns (Y, pAp): Y[j] = A P[j] from the multi-vector K1, pAp[j] = P[j] . Y[j]."""
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        assert P.ndim == 2 and P.shape[1] == self.n(), P.shape
+        k = P.shape[0]
+        Y = np.zeros_like(P)
+        pap = np.zeros(max(k, 1), dtype=np.float64)
+        self._check(lib().cgx_probe_gemv_multi(self._h, int(k), _dp(P), int(P.shape[1]), _dp(Y), int(Y.shape[1]), _dp(pap)))
+        return Y, pap[:k]
 
     # -- stepping interface used by bench.py ----------------------------------------------------------
     def solve_begin(self, x0):

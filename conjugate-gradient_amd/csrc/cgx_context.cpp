@@ -101,6 +101,9 @@ void free_problem(cgx_ctx *ctx)
     ctx->shards.clear();
     (void)hipFree(ctx->d_gathered_ptrs);
     (void)hipFree(ctx->d_scalar_ptrs);
+    (void)hipFree(ctx->multi);
+    ctx->multi = nullptr;
+    ctx->multi_bytes = 0;
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     ctx->h_stage = nullptr;
     ctx->d_gathered_ptrs = nullptr;

@@ -146,6 +146,11 @@ struct cgx_ctx {
     bool steps_ev_pending = false;
     double steps_device_ms = 0;
 
+    // several right-hand sides (cgx_solve_multi, cgx_multi.cpp): ONE device block holding kMaxRhs-wide B, X, R, P[2], Y and the
+    // partials and scalars of the multi kernels, apart from the single path's buffers; made on first use, freed with the problem
+    double *multi = nullptr;
+    size_t multi_bytes = 0;
+
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 
     std::string err;
@@ -269,5 +274,7 @@ cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full);
 cgx_status check_p2p_error(cgx_ctx *ctx);
 cgx_status resident_steps(cgx_ctx *ctx, int nsteps, int *redo);
 void reset_gemv_stats(cgx_ctx *ctx);
+cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out);      // an event of the K1 timing pool
+cgx_status harvest_gemv_events(cgx_ctx *ctx);              // fold the recorded pairs into the K1 statistics (after a sync)
 
 }  // namespace cgxi

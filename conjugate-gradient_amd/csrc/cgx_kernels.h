@@ -356,4 +356,46 @@ hipError_t launch_solve_end(int n, const double *Ax, const double *b, const doub
 hipError_t launch_loopback_gather(double *const *gathered_ptrs, const Scalars *const *scalar_ptrs, int nshards,
                                   hipStream_t s);
 
+// ---- several right-hand sides against one dense matrix, one GPU (cgx_multi.hip) ----------------------------------------------
+// Blocks of vectors are column-major at pitch lda (column j at base + j * lda, zero padded up to lda).  nrhs columns run in the
+// kernels of width multi_width(nrhs) (1, 2, 4, 8 or 16); columns nrhs .. width-1 are masked by nrhs.
+constexpr int kMaxRhs = 16;   // = CGX_MAX_RHS
+struct MultiScalars {
+    double rs[kMaxRhs][2];     // per column: rs[j][k & 1] is rsold of iteration k (as Scalars::rs)
+    int    done[kMaxRhs];      // the column took the break (cg.cc:120-121); nothing writes its x, r, p or scalars afterwards
+    int    k_final[kMaxRhs];   // k of the column's converging iteration
+    int    all_done;           // every column has broken: the host polls this word; later kernels exit at once
+    int    k_all;
+    int    pad[2];
+    double norms[kMaxRhs][3];  // ||Ax - b||^2, ||b||^2, ||x||^2 per column (cg.cc:146-151)
+};
+struct MultiArgs {
+    const double *A;
+    long lda;
+    int n, nrhs;
+    const double *v;           // plain: the vectors; fused: p_old
+    double *p_new;             // fused: p = r + beta p_old, stored once
+    const double *r;           // fused: the residuals
+    const double *rrp;         // fused: K3m's r.r partials, multi_update_grid(n) per column
+    double *Y;                 // A v (live columns only)
+    double *partials;          // multi_gemv_grid(n, width) per column: v_j . Y_j of each workgroup
+    MultiScalars *ms;
+    int k;
+    double tol;
+};
+int multi_width(int nrhs);
+int multi_rows_per_wg(int width);
+int multi_gemv_grid(int n, int width);   // K1m workgroups = p.Ap partials per column
+int multi_update_grid(int n);            // K3m workgroups per column = r.r partials per column
+// K1m: plain (Y = A V) or fused (head of iteration k, P = R + beta P_old, Y = A P); e0 / e1 optional, bound to the dispatch.
+hipError_t launch_multi_gemv(const MultiArgs &g, bool fused, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// K3m: for every live column x += alpha p, r -= alpha Y, r.r partials (grid multi_update_grid(n) x nrhs).
+hipError_t launch_multi_update(int n, long lda, int nrhs, const double *p, const double *Y, const double *partials, int g1, double *x,
+                               double *r, double *rrp, MultiScalars *ms, int parity, hipStream_t s);
+// r = B - Y and r.r partials (set-up); the head of iteration k alone (the loop ran out); the end-of-solve norms.
+hipError_t launch_multi_init(int n, long lda, int nrhs, const double *b, const double *Y, double *r, double *rrp, hipStream_t s);
+hipError_t launch_multi_close(MultiScalars *ms, const double *rrp, int n, int nrhs, int k, double tol, hipStream_t s);
+hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const double *b, const double *x, MultiScalars *ms,
+                              hipStream_t s);
+
 }  // namespace cgx

@@ -1,0 +1,266 @@
+// cgx_multi_host.cpp -- cgx_solve_multi and cgx_probe_gemv_multi: the host side of the multi-vector kernels (cgx_multi.hip).
+//
+// One GPU, dense storage.  The k-wide blocks live in ONE device allocation of the context (cgx_ctx::multi), apart from the single
+// path's per-shard buffers and state blocks, so that a multi solve changes nothing a single solve reads: neither the plan, nor
+// x / r / p, nor the scalar block.  It is made on the first multi call of a problem and freed with the problem.
+#include "cgx_internal.h"
+
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace cgxi;
+
+namespace {
+
+constexpr int kW = cgx::kMaxRhs;
+
+struct MultiView {
+    double *B, *X, *R, *P[2], *Y;   // kW x lda each (column j at + j * lda)
+    double *k1p;                    // kW x multi_gemv_grid(n, 1): K1m's p.Ap partials (grid of the widest-row shape at most)
+    double *rrp;                    // kW x multi_update_grid(n): K3m's r.r partials
+    cgx::MultiScalars *ms;
+};
+
+int k1p_stride(int n)   // the largest K1m grid over the widths
+{
+    int g = 0;
+    for (int w = 1; w <= kW; w *= 2) g = std::max(g, cgx::multi_gemv_grid(n, w));
+    return g;
+}
+
+size_t multi_layout(const cgx_ctx *ctx, double *base, MultiView *v)
+{
+    const size_t vec = (size_t)kW * ctx->lda;
+    size_t off = 0;
+    auto take = [&](size_t count) {
+        double *p = base ? base + off : nullptr;
+        off += (count + 15) / 16 * 16;   // 128-B aligned pieces
+        return p;
+    };
+    v->B = take(vec);
+    v->X = take(vec);
+    v->R = take(vec);
+    v->P[0] = take(vec);
+    v->P[1] = take(vec);
+    v->Y = take(vec);
+    v->k1p = take((size_t)kW * k1p_stride(ctx->n));
+    v->rrp = take((size_t)kW * cgx::multi_update_grid(ctx->n));
+    v->ms = reinterpret_cast<cgx::MultiScalars *>(take((sizeof(cgx::MultiScalars) + 7) / 8));
+    return off * sizeof(double);
+}
+
+// The checks every multi entry point makes, in this order: context, problem, transport and storage, arguments.
+cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in, long ldin, const void *out, long ldout)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    const std::string fn(name);
+    if (!ctx->have_matrix) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no problem set");
+    if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": a cgx_solve_begin / cgx_solve_end pair is open");
+    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->nranks != 1 || ctx->shards.size() != 1)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": one GPU only (CGX_COMM_SELF)");
+    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    if (nrhs < 1 || nrhs > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nrhs must be 1 .. CGX_MAX_RHS");
+    if (!in || !out) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
+    if (ldin < ctx->n || ldout < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");
+    return CGX_OK;
+}
+
+// The context's multi block, made (and zeroed: the pad rows of every vector stay 0) on first use.
+cgx_status ensure_multi(cgx_ctx *ctx, MultiView *v)
+{
+    const size_t bytes = multi_layout(ctx, nullptr, v);
+    if (!ctx->multi) {
+        double *p = nullptr;
+        HIP_TRY(ctx, hipMalloc(&p, bytes));
+        const cgx_status st = [&]() -> cgx_status {
+            HIP_TRY(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+            return CGX_OK;
+        }();
+        if (st != CGX_OK) {
+            (void)hipFree(p);
+            return st;
+        }
+        ctx->multi = p;
+        ctx->multi_bytes = bytes;
+    }
+    multi_layout(ctx, ctx->multi, v);
+    return CGX_OK;
+}
+
+cgx::MultiArgs plain_args(cgx_ctx *ctx, const MultiView &v, int nrhs, const double *vec)
+{
+    cgx::MultiArgs g{};
+    g.A = ctx->shards[0].A;
+    g.lda = ctx->lda;
+    g.n = ctx->n;
+    g.nrhs = nrhs;
+    g.v = vec;
+    g.Y = v.Y;
+    g.partials = v.k1p;
+    g.ms = v.ms;
+    return g;
+}
+
+// host rows (one vector per row, pitch ld) <-> a device block (column j at + j * lda); rows 0 .. n-1 only
+cgx_status upload(cgx_ctx *ctx, double *dst, const double *src, long ld, int nrhs)
+{
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ctx->lda * sizeof(double), src, (size_t)ld * sizeof(double),
+                                  (size_t)ctx->n * sizeof(double), nrhs, hipMemcpyHostToDevice, ctx->stream));
+    return CGX_OK;
+}
+
+cgx_status download(cgx_ctx *ctx, double *dst, long ld, const double *src, int nrhs)
+{
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ld * sizeof(double), src, (size_t)ctx->lda * sizeof(double),
+                                  (size_t)ctx->n * sizeof(double), nrhs, hipMemcpyDeviceToHost, ctx->stream));
+    return CGX_OK;
+}
+
+// K1m fused of iteration k; every `profile_gemv`-th launch is event-timed, the first of the call never (as run_gemv_fused)
+cgx_status run_multi_fused(cgx_ctx *ctx, const MultiView &v, int nrhs, int k)
+{
+    const int every = ctx->cfg.profile_gemv;
+    const long long seq = ctx->gemv_seq++;
+    bool timed = false;
+    if (every > 0 && ctx->ev_used + 2 <= 4096) {
+        if (seq == 0) {
+            timed = ctx->cfg.profile_first != 0;
+            if (!timed) ctx->gemv_discarded++;
+        } else {
+            timed = ((seq - 1) % every) == 0;
+        }
+    }
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (timed) {
+        CGX_TRY(take_event(ctx, &e0));
+        CGX_TRY(take_event(ctx, &e1));
+    }
+    cgx::MultiArgs g = plain_args(ctx, v, nrhs, v.P[k & 1]);
+    g.p_new = v.P[(k + 1) & 1];
+    g.r = v.R;
+    g.rrp = v.rrp;
+    g.k = k;
+    g.tol = ctx->tol;
+    HIP_TRY(ctx, cgx::launch_multi_gemv(g, true, ctx->stream, e0, e1));
+    return CGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
+{
+    CGX_TRY(check_multi(ctx, "cgx_solve_multi", nrhs, B, ldb, X, ldx));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    MultiView v;
+    CGX_TRY(ensure_multi(ctx, &v));
+    hipStream_t st = ctx->stream;
+    const int n = ctx->n;
+    const long lda = ctx->lda;
+    const int g1 = cgx::multi_gemv_grid(n, cgx::multi_width(nrhs));
+    reset_gemv_stats(ctx);
+    const double t_begin = wall_now();
+
+    // set-up, cg.cc:49-92 per column: r = b - A x0, p_old = 0, the r.r partials of iteration 0's head
+    CGX_TRY(upload(ctx, v.B, B, ldb, nrhs));
+    CGX_TRY(upload(ctx, v.X, X, ldx, nrhs));
+    HIP_TRY(ctx, hipMemsetAsync(v.ms, 0, sizeof(cgx::MultiScalars), st));
+    HIP_TRY(ctx, hipMemsetAsync(v.P[0], 0, (size_t)nrhs * lda * sizeof(double), st));
+    HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.X), false, st));
+    HIP_TRY(ctx, cgx::launch_multi_init(n, lda, nrhs, v.B, v.Y, v.R, v.rrp, st));
+
+    // the loop cg.cc:95-137: K1m + K3m per iteration; all_done is polled every check_every iterations, one batch kept queued
+    const double t0 = wall_now();
+    const int every = std::max(1, ctx->cfg.check_every);
+    int k = 0, slot = 0;
+    bool pending[2] = {false, false}, stop = false;
+    while (k < ctx->max_iter && !stop) {
+        const int batch = std::min(ctx->max_iter - k, every);
+        for (int i = 0; i < batch; ++i, ++k) {
+            CGX_TRY(run_multi_fused(ctx, v, nrhs, k));
+            HIP_TRY(ctx, cgx::launch_multi_update(n, lda, nrhs, v.P[(k + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, k & 1, st));
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags + 2 * slot, &v.ms->all_done, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->flag_ev[slot], st));
+        pending[slot] = true;
+        slot ^= 1;
+        if (pending[slot]) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->flag_ev[slot]));
+            pending[slot] = false;
+            if (ctx->h_flags[2 * slot]) stop = true;
+        }
+    }
+    // the head of iteration k for the columns still running (cg.cc:117-121,132), then x and the DEBUG norms (cg.cc:140-151)
+    HIP_TRY(ctx, cgx::launch_multi_close(v.ms, v.rrp, n, nrhs, k, ctx->tol, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    const double t_loop = wall_now() - t0;
+    HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.X), false, st));
+    HIP_TRY(ctx, cgx::launch_multi_norms(n, lda, nrhs, v.Y, v.B, v.X, v.ms, st));
+    cgx::MultiScalars hs;
+    HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ms, sizeof hs, hipMemcpyDeviceToHost, st));
+    CGX_TRY(download(ctx, X, ldx, v.X, nrhs));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
+
+    if (res) {
+        cgx_result base;
+        memset(&base, 0, sizeof base);
+        base.seconds_solve = wall_now() - t_begin;
+        base.seconds_loop = t_loop;
+        base.gemv_launches = ctx->gemv_launches;
+        base.gemv_ms_avg = ctx->gemv_launches ? ctx->gemv_ms_sum / (double)ctx->gemv_launches : 0.0;
+        base.gemv_ms_min = ctx->gemv_ms_min;
+        base.gemv_ms_max = ctx->gemv_ms_max;
+        base.gemv_discarded = ctx->gemv_discarded;
+        if (!ctx->gemv_samples.empty()) {
+            std::vector<float> s(ctx->gemv_samples);
+            const size_t mid = s.size() / 2;
+            std::nth_element(s.begin(), s.begin() + mid, s.end());
+            double med = s[mid];
+            if (s.size() % 2 == 0) med = 0.5 * (med + *std::max_element(s.begin(), s.begin() + mid));
+            base.gemv_ms_median = med;
+        }
+        base.gemv_bytes = 8.0 * ((double)n * n + 2.0 * nrhs * n);
+        for (int j = 0; j < nrhs; ++j) {
+            cgx_result &o = res[j];
+            o = base;
+            const bool done = hs.done[j] != 0;
+            const int k_exit = done ? hs.k_final[j] : k;
+            o.iterations = k_exit;
+            o.converged = done ? 1 : 0;
+            o.residual_prev = std::sqrt(hs.rs[j][k_exit & 1]);          // sqrt(rsold) as printed, cg.cc:152-153
+            o.residual_last = done ? std::sqrt(hs.rs[j][(k_exit + 1) & 1]) : o.residual_prev;
+            o.x_norm = std::sqrt(hs.norms[j][2]);
+            o.rel_residual = std::sqrt(hs.norms[j][0]) / std::sqrt(hs.norms[j][1]);
+        }
+    }
+    return CGX_OK;
+}
+
+cgx_status cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long ldp, double *Y, long ldy, double *pAp)
+{
+    CGX_TRY(check_multi(ctx, "cgx_probe_gemv_multi", nrhs, P, ldp, Y, ldy));
+    if (!pAp) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_gemv_multi: null pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    MultiView v;
+    CGX_TRY(ensure_multi(ctx, &v));
+    const int g1 = cgx::multi_gemv_grid(ctx->n, cgx::multi_width(nrhs));
+    CGX_TRY(upload(ctx, v.P[0], P, ldp, nrhs));
+    HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.P[0]), false, ctx->stream));
+    std::vector<double> parts((size_t)nrhs * g1);
+    HIP_TRY(ctx, hipMemcpyAsync(parts.data(), v.k1p, parts.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    CGX_TRY(download(ctx, Y, ldy, v.Y, nrhs));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int j = 0; j < nrhs; ++j) {   // the workgroups' partials in ascending order
+        double s = 0.0;
+        for (int g = 0; g < g1; ++g) s += parts[(size_t)j * g1 + g];
+        pAp[j] = s;
+    }
+    return CGX_OK;
+}
+
+}  // extern "C"

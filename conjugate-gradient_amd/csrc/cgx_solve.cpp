@@ -104,7 +104,7 @@ cgx_status gather_segments(cgx_ctx *ctx, bool with_tail)
 
 }  // namespace cgxi
 
-namespace {
+namespace cgxi {
 
 // ---- K1 with optional event bracketing -----------------------------------------------------------
 cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)
@@ -117,6 +117,10 @@ cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)
     *out = ctx->ev_pool[ctx->ev_used++];
     return CGX_OK;
 }
+
+}  // namespace cgxi
+
+namespace {
 
 // cfg.profile_update: an event pair for the update kernel of an iteration whose K1 was timed (first shard only: one
 // sample per iteration), or two null handles.

@@ -255,6 +255,23 @@ cgx_status  cgx_get_gemv_samples(cgx_ctx *ctx, double *ms_out, int cap, int *cou
  * `k_update_xr_p2p`, whose duration includes the bounded wait for every peer's chunks (cg.cc:106,135-136). */
 cgx_status  cgx_get_update_samples(cgx_ctx *ctx, double *ms_out, int cap, int *count);
 
+/* ---- several right-hand sides against one matrix (one pass over A per iteration serves all of them) ---- */
+/* nrhs independent copies of cgx_solve's recurrence (cg.cc:96-137) on the current matrix, one per right-hand side: each column
+ * has its own rsold, alpha (with the safeguard of cg.cc:107), beta and break.  A column that breaks keeps its x from then on;
+ * the others go on; the loop ends when every column has broken or after max_iter iterations (cgx_set_tolerance /
+ * cgx_set_max_iter).  Every iteration reads A ONCE for all columns (csrc/cgx_multi.hip; gemv_variant does not apply).
+ * B, X: host arrays, one vector per ROW: B[j*ldb + i], i < n.  X holds the initial guesses on entry and the solutions on return.
+ * res: nrhs results (may be NULL), res[j] as cgx_solve's, rel_residual = ||A x_j - b_j|| / ||b_j||; seconds_* are the same in all
+ * of them, gemv_ms_* (profile_gemv > 0) and cgx_get_gemv_samples describe the multi-vector K1 launches, gemv_bytes =
+ * 8 (n n + 2 nrhs n).  Column j's result depends on (A, b_j, x0_j, nrhs) only: permuting the columns permutes the results bit
+ * for bit.  One GPU (CGX_COMM_SELF) and dense storage only, else CGX_ERR_UNSUPPORTED; nrhs outside 1 .. CGX_MAX_RHS, a null
+ * pointer, ldb < n, ldx < n or no problem set: CGX_ERR_BAD_ARG.  The single path's plan and state are left as they were. */
+#define CGX_MAX_RHS 16
+cgx_status  cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res);
+/* The multi-vector K1 alone (plain form): Y_j = A P_j and pAp[j] = P_j . Y_j from the kernel's per-workgroup partials, added
+ * in ascending order.  P, Y host arrays, one vector per row (P[j*ldp + i]); pAp: nrhs doubles.  Same scope as cgx_solve_multi. */
+cgx_status  cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long ldp, double *Y, long ldy, double *pAp);
+
 /* ---- kernel probes (parity tests of the individual hot ops through the C ABI) ------------- */
 /* Ap = A_shard * p  (K1; cblas_dgemv at cg.cc:101-102) for every local shard; y receives the n
  * results in global row order (LOOPBACK/SELF) or this rank's rows at their global offset (RCCL);
