@@ -342,7 +342,7 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
         if (ctx->mv.tagged) {
             // Tagged words: the plain-double all-gathers of the set-up and verification phases (gather_segments: the initial
             // Ap, the final x) get a slot region of their own behind the tagged one -- channel 0, with its own flag words and
-            // epoch counter -- so that no plain double is ever stored where a tagged reader polls (cgx_kernels.hip "Tagged words").
+            // epoch counter -- so that no plain double is ever stored where a tagged reader polls (cgx_p2p.hip "Tagged words").
             ctx->mv.data_off[0] = off;
             ctx->mv.slot_bytes[0] = ((long)(ctx->seg_Sr + ctx->npart + 1) * 8 + 15) / 16 * 16;
             off += 2L * ctx->nranks * ctx->mv.slot_bytes[0];

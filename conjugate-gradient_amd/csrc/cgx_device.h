@@ -1,6 +1,6 @@
-// cgx_device.h -- device-side helpers shared by the kernel translation units (cgx_kernels.hip, cgx_symv.hip, cgx_resident.hip):
-// the fixed-order reductions, the safeguard of alpha, the tagged-word store, and the iteration head of the per-launch
-// GEMV kernels.  Device code only.
+// cgx_device.h -- device-side helpers shared by the kernel translation units (cgx_kernels.hip, cgx_p2p.hip, cgx_symv.hip,
+// cgx_resident.hip): the fixed-order reductions, the safeguard of alpha, the tagged-word store, the iteration head of the
+// per-launch GEMV kernels, and the chunk arithmetic in front of every multi-rank exchange.  Device code only.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -251,6 +251,46 @@ __device__ __forceinline__ d2 make_p(const SegView &sv, double beta, d2 p_old, i
     p.x = fma(beta, p_old.x, r.x);                                   // cg.cc:127-129
     p.y = fma(beta, p_old.y, r.y);
     return p;
+}
+
+// ------------------------------------------------------------------------------------------------
+// the chunk arithmetic of the multi-rank exchange ("Chunks" in cgx_kernels.hip): k_prefold_ap and the pushers of the
+// fused P2P update (cgx_p2p.hip) call the same functions, so every transport ships the same bits
+// ------------------------------------------------------------------------------------------------
+// Branch-free: every load is unconditional (clamped index, value dropped by a select), so that all of them -- up to
+// kMaxSplit pieces and the two elements of p -- are in flight together; loads behind a branch or in a loop of unknown
+// length are waited for one by one (seen in the ISA: s_waitcnt vmcnt(0) after each piece).
+constexpr int kMaxSplit = 8;
+__device__ __forceinline__ d2 chunk_pair(const double *__restrict__ parts, int split, long stride, int row, int Sr)
+{
+    const int rc = row < Sr ? row : Sr - 2;                           // Sr is even and >= 2, slices are 16-B aligned
+    d2 v[kMaxSplit];
+#pragma unroll
+    for (int sp = 0; sp < kMaxSplit; ++sp)
+        v[sp] = *reinterpret_cast<const d2 *>(parts + (sp < split ? sp : split - 1) * stride + rc);
+    d2 a = v[0];
+#pragma unroll
+    for (int sp = 1; sp < kMaxSplit; ++sp) {                          // ascending piece order
+        a.x = sp < split ? a.x + v[sp].x : a.x;
+        a.y = sp < split ? a.y + v[sp].y : a.y;
+    }
+    if (row >= Sr) a = d2{0.0, 0.0};
+    return a;
+}
+
+// the pair's two elements of p_sub (p_loc = p_new + row0; row0 may be odd: 8-B loads), 0 behind the last row
+__device__ __forceinline__ d2 chunk_p(const double *__restrict__ p_loc, int row, int rows)
+{
+    const int last = rows > 0 ? rows - 1 : 0;                         // rows == 0: p_loc[0] is still inside p (zero pad)
+    const double p0 = p_loc[row < rows ? row : last];
+    const double p1 = p_loc[row + 1 < rows ? row + 1 : last];
+    return d2{row < rows ? p0 : 0.0, row + 1 < rows ? p1 : 0.0};
+}
+
+template <int WAVES>
+__device__ __forceinline__ double chunk_dot(d2 p, d2 a, double *lds)
+{
+    return block_sum<WAVES>(fma(p.y, a.y, p.x * a.x), lds);
 }
 
 }  // namespace cgx

@@ -1,5 +1,5 @@
 // cgx_kernels.h -- launch interface of the CDNA4 (gfx950) kernels of the CG hot path.
-// The host code (cgx_context / cgx_matrix / cgx_solve / cgx_probe .cpp) sees only these plain functions; all device code is in cgx_kernels.hip.
+// The host code (cgx_context / cgx_matrix / cgx_solve / cgx_probe .cpp) sees only these plain functions; all device code is in the .hip files.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -231,7 +231,7 @@ struct MailboxView {
     long slot_bytes[kP2pChannels];       // bytes per (parity, rank) slot
     int nranks, rank;
     int tagged;                          // 1 = the fused update hands its bytes over as tagged words (no flags, no fences;
-                                         // cgx_kernels.hip "Tagged words"); slots of channel 1 are then twice as large
+                                         // cgx_p2p.hip "Tagged words"); slots of channel 1 are then twice as large
     int acquire;                         // 1 = one system-scope acquire fence per workgroup behind the flag wait of
                                          // k_update_xr_p2p (default); 0 only for the A/B of its cost (tools/p2p_one_rank.py)
 };
@@ -255,8 +255,9 @@ hipError_t launch_update_xr_p2p(int n, int rows, int row0, const double *p_new, 
                                 int parity, long long timeout_ticks, int *err, hipStream_t s,
                                 const double *ap_src, int split, long stride, hipEvent_t e_start = nullptr,
                                 hipEvent_t e_stop = nullptr);
-// The exchange of launch_update_xr_p2p alone (the same device code), on caller data: vals[i] = the Ap element read for
-// global row i (n doubles), sums[wg] = the folded chunk partials as workgroup wg saw them (update_xr_grid(n) doubles).
+// The exchange of launch_update_xr_p2p alone (the same kernel template, SELFTEST = true), on caller data: vals[i] = the Ap
+// element read for global row i (n doubles), sums[wg] = the folded chunk partials as workgroup wg saw them
+// (update_xr_grid(n) doubles).
 hipError_t launch_chunk_exchange_selftest(int n, int rows, int row0, const double *p_like, SegView apv, int cpr,
                                           const MailboxView &mv, int chan, unsigned long long epoch, long long timeout_ticks,
                                           int *err, const double *ap_src, int split, long stride, double *vals, double *sums,

@@ -16,7 +16,7 @@
 //   K3 update_xr    p.Ap = fixed-order sum of all ranks' partials; alpha         cg.cc:107
 //                   x_sub += alpha p_sub                                         cg.cc:110
 //                   r -= alpha Ap for ALL n rows (r is replicated); r.r          cg.cc:113,116
-//   [CGX_COMM_P2P: Kp, the exchange and K3 are ONE kernel, k_update_xr_p2p (flag words) / k_update_xr_p2p_tagged]
+//   [CGX_COMM_P2P: Kp, the exchange and K3 are ONE kernel, k_update_xr_p2p in cgx_p2p.hip (flag words or tagged words)]
 //
 // What travels between ranks is Ap, not p: r and p are replicated, every rank updates the whole r from the
 // gathered Ap and reduces r.r over all n rows in the same fixed order, so r.r is bit-identical on every
@@ -417,44 +417,9 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv_ldsp(const double *__restri
 // in one fixed order.  What travels between ranks is then [Ap slice | one p.Ap partial per chunk]: n/512 partials in all,
 // whatever the grid of K1 was -- K1's own per-workgroup partials (4096 per rank with the columns split 8 ways) are not
 // folded by anybody on a multi-GPU run.  Used by k_prefold_ap (RCCL, separate mailbox exchange, loopback) and by the
-// pushers of k_update_xr_p2p (fused exchange): the same code, the same bits on every transport.
+// pushers of k_update_xr_p2p (fused exchange, cgx_p2p.hip): the same code (chunk_pair / chunk_p / chunk_dot, cgx_device.h),
+// the same bits on every transport.
 // ------------------------------------------------------------------------------------------------
-// Branch-free: every load is unconditional (clamped index, value dropped by a select), so that all of them -- up to
-// kMaxSplit pieces and the two elements of p -- are in flight together; loads behind a branch or in a loop of unknown
-// length are waited for one by one (seen in the ISA: s_waitcnt vmcnt(0) after each piece).
-constexpr int kMaxSplit = 8;
-__device__ __forceinline__ d2 chunk_pair(const double *__restrict__ parts, int split, long stride, int row, int Sr)
-{
-    const int rc = row < Sr ? row : Sr - 2;                           // Sr is even and >= 2, slices are 16-B aligned
-    d2 v[kMaxSplit];
-#pragma unroll
-    for (int sp = 0; sp < kMaxSplit; ++sp)
-        v[sp] = *reinterpret_cast<const d2 *>(parts + (sp < split ? sp : split - 1) * stride + rc);
-    d2 a = v[0];
-#pragma unroll
-    for (int sp = 1; sp < kMaxSplit; ++sp) {                          // ascending piece order
-        a.x = sp < split ? a.x + v[sp].x : a.x;
-        a.y = sp < split ? a.y + v[sp].y : a.y;
-    }
-    if (row >= Sr) a = d2{0.0, 0.0};
-    return a;
-}
-
-// the pair's two elements of p_sub (p_loc = p_new + row0; row0 may be odd: 8-B loads), 0 behind the last row
-__device__ __forceinline__ d2 chunk_p(const double *__restrict__ p_loc, int row, int rows)
-{
-    const int last = rows > 0 ? rows - 1 : 0;                         // rows == 0: p_loc[0] is still inside p (zero pad)
-    const double p0 = p_loc[row < rows ? row : last];
-    const double p1 = p_loc[row + 1 < rows ? row + 1 : last];
-    return d2{row < rows ? p0 : 0.0, row + 1 < rows ? p1 : 0.0};
-}
-
-template <int WAVES>
-__device__ __forceinline__ double chunk_dot(d2 p, d2 a, double *lds)
-{
-    return block_sum<WAVES>(fma(p.y, a.y, p.x * a.x), lds);
-}
-
 // One workgroup per chunk, in front of the exchange: dst = the Ap slice of this rank's segment, tail = its chunk partials.
 __global__ __launch_bounds__(256) void k_prefold_ap(const double *__restrict__ parts, int split, long stride, int rows, int Sr,
                                                      const double *__restrict__ p_loc, double *__restrict__ dst,
@@ -1073,470 +1038,6 @@ __global__ __launch_bounds__(256) void k_coo_assign(double *__restrict__ cells, 
 }
 
 // ------------------------------------------------------------------------------------------------
-// Direct peer exchange over xGMI: replaces one RCCL all-gather launch.
-// Protocol per (channel, epoch), placement independent:
-//   producer: plain 16-B stores of the payload into the PEER's mailbox slot [epoch&1][my rank]; every storing
-//             thread fences at system scope; workgroup barrier; one lane stores flag = epoch with a system-scope
-//             release atomic into the peer's flag word [channel][my rank];
-//   consumer: one lane polls its OWN flag word [channel][peer] with system-scope acquire loads (bounded by the
-//             100 MHz wall clock), workgroup barrier, every thread fences (acquire, system) and reads the slot
-//             with system-scope loads (never served from a stale cache line), then plain-stores into the
-//             ordinary working buffer the next kernel reads.
-// Two parities suffice: a rank can start epoch e+2 only after every peer delivered e+1, which a peer does only
-// after the kernel that consumed epoch e on that peer has finished (stream order).
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_mailbox_allgather(MailboxView mv, int chan, unsigned long long epoch,
-                                                            const double *__restrict__ src, int count, int tail_off,
-                                                            int tail_n, double *__restrict__ dst, long dst_stride,
-                                                            int sum_off, int copy_self, long long timeout_ticks, int *err)
-{
-    const int peer = blockIdx.x;
-    const int tid = threadIdx.x;
-    // an earlier wait expired: do not wait again, let the host see it.  Decided per workgroup (another workgroup may
-    // raise the word while this one starts), so that no thread is left alone at a barrier.
-    if (__syncthreads_or(__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) return;
-    __shared__ double lds[4];
-    double tail_sum = 0.0;
-    if (tail_n > 0) {
-        // fold my tail (the K1 partials) in a fixed order and ship ONE double behind the main payload (every
-        // workgroup computes the same bits): the local half of MPI_Allreduce (cg.cc:106) rides in the exchange
-        double v = 0.0;
-        for (int i = tid; i < tail_n; i += 256) v += src[tail_off + i];
-        tail_sum = block_sum<4>(v, lds);
-    }
-    if (peer == mv.rank) {
-        if (copy_self)
-            for (int i = tid; i < count; i += 256) dst[(long)mv.rank * dst_stride + i] = src[i];
-        if (tail_n > 0 && tid == 0) dst[(long)mv.rank * dst_stride + sum_off] = tail_sum;
-        return;
-    }
-    const int parity = (int)(epoch & 1);
-    const long slot = mv.slot_bytes[chan];
-    // ---- push my contribution into the peer's mailbox: [count doubles | tail sum] ----------------------------
-    {
-        double *out = reinterpret_cast<double *>(mv.base[peer] + mv.data_off[chan] +
-                                                 ((long)parity * mv.nranks + mv.rank) * slot);
-        const int pairs = count >> 1;
-        for (int i = tid; i < pairs; i += 256)
-            *reinterpret_cast<d2 *>(out + 2 * i) = *reinterpret_cast<const d2 *>(src + 2 * i);
-        if ((count & 1) && tid == 0) out[count - 1] = src[count - 1];
-        if (tail_n > 0 && tid == 0) out[count] = tail_sum;
-        __threadfence_system();   // every storing wave: write back, wait for its own stores (vmcnt is per wave), before the barrier
-        __syncthreads();
-        if (tid == 0) {
-            unsigned long long *flag = reinterpret_cast<unsigned long long *>(
-                mv.base[peer] + ((long)chan * kMaxRanks + mv.rank) * kP2pFlagStride);
-            // the same tail as chunk_publish: release fence, its own wait (the compiler drops the one behind buffer_wbl2 when it
-            // can prove this wave has nothing outstanding -- harmless here, every wave has drained above, but not left to that),
-            // then the flag as a relaxed system-scope store
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __hip_atomic_store(flag, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        }
-    }
-    // ---- wait for the peer's contribution in MY mailbox, then copy it out ------------------------------------
-    __shared__ int s_ok;
-    if (tid == 0) {
-        const unsigned long long *flag = reinterpret_cast<const unsigned long long *>(
-            mv.base[mv.rank] + ((long)chan * kMaxRanks + peer) * kP2pFlagStride);
-        const long long t0 = wall_clock64();
-        int ok = 1;
-        while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < epoch) {   // relaxed polls, ONE acquire after
-            __builtin_amdgcn_s_sleep(8);
-            if (wall_clock64() - t0 > timeout_ticks) {   // every spin is bounded: give up, tell the host
-                ok = 0;
-                atomicExch(err, 1);
-                break;
-            }
-        }
-        s_ok = ok;
-    }
-    __syncthreads();
-    if (!s_ok) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");   // system scope
-    {
-        const unsigned long long *in = reinterpret_cast<const unsigned long long *>(
-            mv.base[mv.rank] + mv.data_off[chan] + ((long)parity * mv.nranks + peer) * slot);
-        double *out = dst + (long)peer * dst_stride;
-        const int total = count + (tail_n > 0 ? 1 : 0);
-        // 8 independent loads in flight per thread: the slot is read straight from memory, never from a cache
-        for (int base = 0; base < total; base += 8 * 256) {
-            unsigned long long v[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = base + u * 256 + tid;
-                v[u] = (i < total) ? __hip_atomic_load(in + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : 0ull;
-            }
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                const int i = base + u * 256 + tid;
-                if (i < count) out[i] = __longlong_as_double((long long)v[u]);
-                else if (i == count && tail_n > 0) out[sum_off] = __longlong_as_double((long long)v[u]);
-            }
-        }
-    }
-}
-
-// ------------------------------------------------------------------------------------------------
-// K3 with the exchange inside (CGX_COMM_P2P): iteration = K1 + this kernel, nothing else.
-// The (peer, chunk) pairs -- P x cpr of them, about as many as the kernel has workgroups -- are dealt over the grid: a
-// workgroup adds K1's column pieces for ONE chunk of kChunkRows rows, reduces the chunk's p.Ap partial, stores
-// [chunk of Ap | partial] into ONE peer's mailbox slot (its own included: own rows take the same road as everybody
-// else's) and raises that peer's flag word (me, chunk): one pass of independent loads, one 16-B store per thread, one fence,
-// one flag.  (Round 2 had P workgroups push a whole slice each: 8 dependent rounds of loads per pusher, and every
-// workgroup folded all of the rank's K1 partials -- 4096 with the columns split 8 ways: 13.4 us against 6.7 unsplit.)
-// Then EVERY workgroup waits (bounded) for all P x cpr flags in its own mailbox, lane f polling word f, and reads what
-// it needs straight from the slots with system-scope loads: the P x cpr partials, folded in one fixed order (bit-identical
-// on every rank, MPI_Allreduce cg.cc:106), and per thread the one Ap element of its row.  No copy-out pass, no kernel
-// boundary between exchange and update.  All workgroups must be co-resident (the host checks the occupancy): pushers
-// never wait before they have pushed, so every flag a workgroup polls is raised by a workgroup that is running.
-// ------------------------------------------------------------------------------------------------
-// The exchange half of that kernel as device functions, so that the self-test of the transport (k_chunk_exchange_selftest,
-// the gate in front of every P2P run) executes EXACTLY the stores, fences, flag words, polls and loads of the production
-// kernel, not a look-alike.
-struct ChunkItem {      // one (peer, chunk) pair of this workgroup, loads issued
-    int peer, c, row;
-    d2 a, pp;
-};
-
-__device__ __forceinline__ ChunkItem chunk_fetch(int pr, int cpr, const double *__restrict__ ap_src, int split, long part_stride,
-                                                 int Sr, const double *__restrict__ p_loc, int rows)
-{
-    ChunkItem it;
-    it.peer = pr / cpr;
-    it.c = pr - it.peer * cpr;
-    it.row = (it.c * 256 + (int)threadIdx.x) * 2;                     // this thread's pair of rows of MY slice
-    it.pp = chunk_p(p_loc, it.row, rows);
-    it.a = chunk_pair(ap_src, split, part_stride, it.row, Sr);
-    return it;
-}
-
-// [chunk of Ap | its p.Ap partial] into the peer's slot, then the peer's flag word (me, chunk).
-// Release, the producer form of the guide (MI355X_MICROARCH.md, "Valid forms"): EVERY storing wave waits for its own stores
-// (`s_waitcnt vmcnt(0)`: the counter is per wave, and neither a barrier nor a workgroup-scope release drains it), then the
-// workgroup barrier, then lane 0: one system-scope release fence, its own vmcnt(0), and the flag as a relaxed system-scope
-// store.  (Round 3 had only the barrier and a release STORE by lane 0: in the ISA waves 1-3 went from their
-// global_store_dwordx4 straight to s_barrier, so over xGMI the flag could have passed their part of the chunk -- the
-// one-GPU self-test cannot see that; found by review)
-__device__ __forceinline__ void chunk_publish(const MailboxView &mv, int chan, unsigned long long epoch, int cpr, int Sr,
-                                              const ChunkItem &it, double *lds)
-{
-    const int P = mv.nranks, me = mv.rank, par = (int)(epoch & 1);
-    const double d = chunk_dot<4>(it.pp, it.a, lds);                  // local part of MPI_Allreduce(p.Ap), cg.cc:105-106
-    double *out = reinterpret_cast<double *>(mv.base[it.peer] + mv.data_off[chan] + ((long)par * P + me) * mv.slot_bytes[chan]);
-    if (it.row < Sr) *reinterpret_cast<d2 *>(out + it.row) = it.a;
-    if (threadIdx.x == 0) out[Sr + it.c] = d;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                  // this wave's stores have been acknowledged
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "");                 // system scope
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __hip_atomic_store(reinterpret_cast<unsigned long long *>(mv.base[it.peer] + mv.cflag_off) + (me * cpr + it.c), epoch,
-                           __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    }
-}
-
-// Lane f waits for flag word f = (source rank, chunk) of MY mailbox (bounded by the 100 MHz wall clock), then ONE
-// system-scope acquire per polling wave, drained before the caller's barrier releases the other waves (the consumer form of
-// the guide: relaxed polls -> one acquire -> s_waitcnt vmcnt(0) -> barrier -> loads).  Every load of handed-off bytes
-// afterwards is a system-scope load as well, so nothing rests on one mechanism alone when the peer's stores arrive over
-// xGMI instead of from a process on the same GPU.  Returns 0 in the lanes whose wait expired.
-__device__ __forceinline__ int chunk_wait_all(const MailboxView &mv, unsigned long long epoch, int npairs, long long timeout_ticks,
-                                              int *err)
-{
-    int ok = 1;
-    const unsigned long long *flags = reinterpret_cast<const unsigned long long *>(mv.base[mv.rank] + mv.cflag_off);
-    for (int f = threadIdx.x; f < npairs; f += 256) {
-        const long long t0 = wall_clock64();
-        // relaxed polls (an acquire per poll would invalidate caches every time round: 2-3x slower per hop)
-        while (__hip_atomic_load(flags + f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) < epoch) {
-            __builtin_amdgcn_s_sleep(4);
-            if (wall_clock64() - t0 > timeout_ticks) {
-                ok = 0;
-                atomicExch(err, 1);
-                break;
-            }
-        }
-    }
-    if (mv.acquire && ((int)threadIdx.x & ~63) < npairs) {
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "");
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    }
-    return ok;
-}
-
-__device__ __forceinline__ const unsigned long long *chunk_slot(const MailboxView &mv, int chan, unsigned long long epoch, int q)
-{
-    return reinterpret_cast<const unsigned long long *>(mv.base[mv.rank] + mv.data_off[chan]) +
-           ((long)(epoch & 1) * mv.nranks + q) * (mv.slot_bytes[chan] / 8);
-}
-
-// this thread's share of all ranks' chunk partials, one fixed order (the caller block-reduces)
-__device__ __forceinline__ double chunk_read_partials(const MailboxView &mv, int chan, unsigned long long epoch, int cpr, int Sr,
-                                                      int npairs)
-{
-    double cs = 0.0;
-    for (int f = threadIdx.x; f < npairs; f += 256) {
-        const int q = f / cpr, c = f - q * cpr;
-        cs += __longlong_as_double((long long)__hip_atomic_load(chunk_slot(mv, chan, epoch, q) + Sr + c, __ATOMIC_RELAXED,
-                                                                  __HIP_MEMORY_SCOPE_SYSTEM));
-    }
-    return cs;
-}
-
-__device__ __forceinline__ double chunk_read_ap(const MailboxView &mv, int chan, unsigned long long epoch, int q, int off)
-{
-    return __longlong_as_double((long long)__hip_atomic_load(chunk_slot(mv, chan, epoch, q) + off, __ATOMIC_RELAXED,
-                                                              __HIP_MEMORY_SCOPE_SYSTEM));
-}
-
-__global__ __launch_bounds__(256) void k_update_xr_p2p(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                        SegView apv, int cpr, MailboxView mv, int chan,
-                                                        unsigned long long epoch, double *__restrict__ x, SegView rv,
-                                                        Scalars *sc, int parity_rs, long long timeout_ticks, int *err,
-                                                        const double *__restrict__ ap_src, int split, long part_stride)
-{
-    __shared__ double lds[4];
-    double *r = rv.base;
-    const int tid = threadIdx.x, P = mv.nranks;
-    const int done = sc->done;
-    // (an atomic load, not a volatile one: the compiler waits for a volatile load on the spot -- a whole memory round trip
-    // at the top of the kernel with nothing else in flight, seen in the ISA)
-    const int had_err = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const double rsold = sc->rs[parity_rs];
-    const int i = blockIdx.x * 256 + tid;   // global row
-    const int li = i - row0;
-    const bool in = i < n, own = in && li >= 0 && li < rows;
-    double r_i = 0.0, p_i = 0.0, x_i = 0.0;
-    if (in) r_i = r[i];
-    if (own) { p_i = p_new[i]; x_i = x[li]; }
-    const int npairs = P * cpr;
-    // the first (peer, chunk) pair of this workgroup: its loads go out with the ones above, ahead of the first wait
-    int pr = blockIdx.x;
-    ChunkItem it{};
-    if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_new + row0, rows);   // uniform per workgroup
-    // `done` is identical on every rank (r.r is bit-identical), so either all ranks exchange or none does
-    if (__syncthreads_or(done | had_err)) return;
-    while (pr < npairs) {
-        chunk_publish(mv, chan, epoch, cpr, apv.Sr, it, lds);
-        pr += gridDim.x;
-        if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_new + row0, rows);
-    }
-    const int ok = chunk_wait_all(mv, epoch, npairs, timeout_ticks, err);
-    if (!__syncthreads_and(ok)) return;
-    // the row's Ap element first, the partials behind it: both loads are in flight together (the other way round the
-    // partial is consumed -- waited for -- before the Ap load is even issued: one more memory round trip for wave 0)
-    double ap_i = 0.0;
-    if (in) {
-        const int q = (P > 1) ? seg_owner(apv, i) : 0;
-        ap_i = chunk_read_ap(mv, chan, epoch, q, i - q * apv.n_loc);
-    }
-    const double cs = chunk_read_partials(mv, chan, epoch, cpr, apv.Sr, npairs);
-    const double conj = block_sum<4>(cs, lds);                       // bit-identical on every rank (cg.cc:106)
-    const double alpha = safeguarded_alpha(rsold, conj);             // cg.cc:107
-    double rr = 0.0;
-    if (in) {
-        const double rn = fma(-alpha, ap_i, r_i);                     // cg.cc:113
-        r[i] = rn;
-        rr = rn * rn;                                                 // cg.cc:116
-    }
-    if (own) x[li] = fma(alpha, p_i, x_i);                            // cg.cc:110
-    rr = block_sum<4>(rr, lds);
-    if (tid == 0) r[rv.Sr + blockIdx.x] = rr;
-}
-
-// ------------------------------------------------------------------------------------------------
-// Tagged words: the exchange without flags and without fences (cfg.p2p_tagged; the transport self-test decides whether a
-// node may use it).  Every double travels as two 8-byte words {32 bits of the value | 32 bits of the epoch}, each written
-// with ONE relaxed system-scope atomic store and read with relaxed system-scope atomic loads.  A reader that sees the
-// epoch in a word knows that the word's other half belongs to the same store (8-byte atomics are single-copy atomic), and
-// it needs nothing else: no word depends on the order in which any other word arrives, so there is no release, no flag,
-// no acquire, and no barrier between "the data is there" and "use it" -- the chain is store -> (xGMI) -> the poll that
-// hits.  A slot still holds the words of epoch e-2 until they are overwritten: the tag is compared for equality.
-// What a tagged slot can hold, and why none of it passes for the current epoch (round 4):
-//   * zeros -- the mailbox is zero-filled when it is created, and the tagged region is zero-filled again whenever it is laid
-//     out anew (a new problem geometry, the self-test): p2p_tag() is never 0;
-//   * tagged words of epoch e-2, e-4, ... of the SAME layout -- every position a reader looks at is rewritten in every
-//     epoch of its parity, so the newest stale tag is that of e-2, and p2p_tag(e) != p2p_tag(e-2) for every e;
-//   * nothing else: the plain-double all-gathers of the set-up and verification phases (k_mailbox_allgather: x0 / x /
-//     the initial Ap) have a slot region and an epoch counter of their own in tagged mode (channel 0), so no plain double is
-//     ever stored where a tagged reader polls.  (Round 3 shared channel 1 and relied on "no finite double looks like a tag
-//     during the first 2^19 epochs of a context".)
-// Twice the bytes on the wire (64 KiB per rank at N = 32768): irrelevant for a latency-bound exchange.
-// ------------------------------------------------------------------------------------------------
-// polls both words until they carry `tag` (bounded by the wall clock); *ok = 0 if the wait expired
-__device__ __forceinline__ double tagged_load(const unsigned long long *src, unsigned tag, long long timeout_ticks, int *err, int *ok)
-{
-    const long long t0 = wall_clock64();
-    unsigned long long w0, w1;
-    for (;;) {
-        w0 = __hip_atomic_load(src, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        w1 = __hip_atomic_load(src + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if ((unsigned)(w0 >> 32) == tag && (unsigned)(w1 >> 32) == tag) break;
-        __builtin_amdgcn_s_sleep(2);
-        if (wall_clock64() - t0 > timeout_ticks) {
-            *ok = 0;
-            atomicExch(err, 1);
-            break;
-        }
-    }
-    return __longlong_as_double((long long)((w0 & 0xffffffffull) | (w1 << 32)));
-}
-
-__device__ __forceinline__ unsigned long long *tagged_slot(const MailboxView &mv, int owner, int chan, unsigned long long epoch, int q)
-{
-    return reinterpret_cast<unsigned long long *>(mv.base[owner] + mv.data_off[chan] +
-                                                  ((long)(epoch & 1) * mv.nranks + q) * mv.slot_bytes[chan]);
-}
-
-// The tagged-word form of k_update_xr_p2p: same pairs, same chunk arithmetic (chunk_pair / chunk_dot: the same bits), same
-// fold order of the partials; only how the bytes are handed over differs.
-template <bool SELFTEST>
-__global__ __launch_bounds__(256) void k_update_xr_p2p_tagged(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                               SegView apv, int cpr, MailboxView mv, int chan,
-                                                               unsigned long long epoch, double *__restrict__ x, SegView rv,
-                                                               Scalars *sc, int parity_rs, long long timeout_ticks, int *err,
-                                                               const double *__restrict__ ap_src, int split, long part_stride,
-                                                               double *__restrict__ vals, double *__restrict__ sums)
-{
-    __shared__ double lds[4];
-    const int tid = threadIdx.x, P = mv.nranks, me = mv.rank;
-    const unsigned tag = p2p_tag(epoch);
-    int done = 0;
-    double rsold = 0.0, r_i = 0.0, p_i = 0.0, x_i = 0.0;
-    const int had_err = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int i = blockIdx.x * 256 + tid;   // global row
-    const int li = i - row0;
-    const bool in = i < n, own = in && li >= 0 && li < rows;
-    if constexpr (!SELFTEST) {
-        done = sc->done;
-        rsold = sc->rs[parity_rs];
-        if (in) r_i = rv.base[i];
-        if (own) { p_i = p_new[i]; x_i = x[li]; }
-    }
-    const int npairs = P * cpr;
-    int pr = blockIdx.x;
-    ChunkItem it{};
-    if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_new + row0, rows);
-    if (__syncthreads_or(done | had_err)) return;
-    while (pr < npairs) {
-        const double d = chunk_dot<4>(it.pp, it.a, lds);
-        unsigned long long *out = tagged_slot(mv, it.peer, chan, epoch, me);
-        {
-            // A lane holds the pair of rows (2L, 2L+1) of its wave's 128 rows; transposed through the wave so that one store
-            // instruction covers 64 consecutive elements = 1 KiB without holes (whole 64-byte requests instead of half-masked
-            // ones): lane L stores element L, then element 64 + L.
-            const int lane = tid & 63, src = lane >> 1;
-            const bool odd = (lane & 1) != 0;
-            const double x1 = __shfl(it.a.x, src, 64), y1 = __shfl(it.a.y, src, 64);
-            const double x2 = __shfl(it.a.x, 32 + src, 64), y2 = __shfl(it.a.y, 32 + src, 64);
-            const int row_a = it.row - 2 * lane + lane, row_b = row_a + 64;
-            if (row_a < apv.Sr) tagged_store(out + 2 * row_a, odd ? y1 : x1, tag);
-            if (row_b < apv.Sr) tagged_store(out + 2 * row_b, odd ? y2 : x2, tag);
-        }
-        if (tid == 0) tagged_store(out + 2 * (apv.Sr + it.c), d, tag);
-        pr += gridDim.x;
-        if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_new + row0, rows);
-    }
-    // Every thread polls the two words of its own Ap element and -- the first P*cpr threads -- of one chunk partial, both in
-    // the same loop: all four loads of a round are in flight together (one after the other, the first wave of every
-    // workgroup paid two memory round trips where one does).
-    int ok = 1;
-    double cs = 0.0, ap_i = 0.0;
-    {
-        const unsigned long long *wa = nullptr, *wp = nullptr;
-        if (in) {
-            const int q = (P > 1) ? seg_owner(apv, i) : 0;
-            wa = tagged_slot(mv, me, chan, epoch, q) + 2 * (i - q * apv.n_loc);
-        }
-        if (tid < npairs) {
-            const int q = tid / cpr, c = tid - q * cpr;
-            wp = tagged_slot(mv, me, chan, epoch, q) + 2 * (apv.Sr + c);
-        }
-        const unsigned long long *dummy = tagged_slot(mv, me, chan, epoch, 0);   // a mapped address for the loads nobody needs
-        bool need_a = wa != nullptr, need_p = wp != nullptr;
-        const long long t0 = wall_clock64();
-        while (need_a || need_p) {
-            const unsigned long long *pa = need_a ? wa : dummy, *pp = need_p ? wp : dummy;
-            const unsigned long long a0 = __hip_atomic_load(pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const unsigned long long a1 = __hip_atomic_load(pa + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const unsigned long long p0 = __hip_atomic_load(pp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            const unsigned long long p1 = __hip_atomic_load(pp + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-            if (need_a && (unsigned)(a0 >> 32) == tag && (unsigned)(a1 >> 32) == tag) {
-                ap_i = __longlong_as_double((long long)((a0 & 0xffffffffull) | (a1 << 32)));
-                need_a = false;
-            }
-            if (need_p && (unsigned)(p0 >> 32) == tag && (unsigned)(p1 >> 32) == tag) {
-                cs = __longlong_as_double((long long)((p0 & 0xffffffffull) | (p1 << 32)));
-                need_p = false;
-            }
-            if (!(need_a || need_p)) break;
-            __builtin_amdgcn_s_sleep(2);
-            if (wall_clock64() - t0 > timeout_ticks) {               // bounded: give up, tell the host
-                ok = 0;
-                atomicExch(err, 1);
-                break;
-            }
-        }
-        for (int f = tid + 256; f < npairs; f += 256) {              // more than 256 partials (n > 131072): the rest, same order
-            const int q = f / cpr, c = f - q * cpr;
-            cs += tagged_load(tagged_slot(mv, me, chan, epoch, q) + 2 * (apv.Sr + c), tag, timeout_ticks, err, &ok);
-        }
-    }
-    if (!__syncthreads_and(ok)) return;
-    const double conj = block_sum<4>(cs, lds);                       // bit-identical on every rank (cg.cc:106)
-    if constexpr (SELFTEST) {
-        if (in) vals[i] = ap_i;
-        if (tid == 0) sums[blockIdx.x] = conj;
-    } else {
-        const double alpha = safeguarded_alpha(rsold, conj);         // cg.cc:107
-        double rr = 0.0;
-        if (in) {
-            const double rn = fma(-alpha, ap_i, r_i);                 // cg.cc:113
-            rv.base[i] = rn;
-            rr = rn * rn;                                             // cg.cc:116
-        }
-        if (own) x[li] = fma(alpha, p_i, x_i);                        // cg.cc:110
-        rr = block_sum<4>(rr, lds);
-        if (tid == 0) rv.base[rv.Sr + blockIdx.x] = rr;
-    }
-}
-
-// The exchange of k_update_xr_p2p alone, on a pattern: every thread stores the Ap element it read for its row to
-// vals[i], every workgroup the folded partials to sums[blockIdx.x].  cgx_p2p_selftest compares both with what every rank
-// must have sent.
-__global__ __launch_bounds__(256) void k_chunk_exchange_selftest(int n, int rows, int row0, const double *__restrict__ p_like,
-                                                                  SegView apv, int cpr, MailboxView mv, int chan,
-                                                                  unsigned long long epoch, long long timeout_ticks, int *err,
-                                                                  const double *__restrict__ ap_src, int split, long part_stride,
-                                                                  double *__restrict__ vals, double *__restrict__ sums)
-{
-    __shared__ double lds[4];
-    const int tid = threadIdx.x, P = mv.nranks;
-    const int had_err = __hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const int i = blockIdx.x * 256 + tid;
-    const int npairs = P * cpr;
-    int pr = blockIdx.x;
-    ChunkItem it{};
-    if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_like + row0, rows);
-    if (__syncthreads_or(had_err)) return;
-    while (pr < npairs) {
-        chunk_publish(mv, chan, epoch, cpr, apv.Sr, it, lds);
-        pr += gridDim.x;
-        if (pr < npairs) it = chunk_fetch(pr, cpr, ap_src, split, part_stride, apv.Sr, p_like + row0, rows);
-    }
-    const int ok = chunk_wait_all(mv, epoch, npairs, timeout_ticks, err);
-    if (!__syncthreads_and(ok)) return;
-    const double cs = chunk_read_partials(mv, chan, epoch, cpr, apv.Sr, npairs);
-    if (i < n) {
-        const int q = (P > 1) ? seg_owner(apv, i) : 0;
-        vals[i] = chunk_read_ap(mv, chan, epoch, q, i - q * apv.n_loc);
-    }
-    const double conj = block_sum<4>(cs, lds);
-    if (tid == 0) sums[blockIdx.x] = conj;
-}
-
-// ------------------------------------------------------------------------------------------------
 // host-side launchers
 // ------------------------------------------------------------------------------------------------
 static inline int ceil_div(long a, long b) { return (int)((a + b - 1) / b); }
@@ -1890,54 +1391,6 @@ hipError_t launch_dia_pack(const double *A, long lda, int n, int row0, int rows,
     return hipGetLastError();
 }
 
-hipError_t launch_update_xr_p2p(int n, int rows, int row0, const double *p_new, SegView apv, int cpr,
-                                const MailboxView &mv, int chan, unsigned long long epoch, double *x, SegView rv, Scalars *sc,
-                                int parity, long long timeout_ticks, int *err, hipStream_t s, const double *ap_src, int split,
-                                long stride, hipEvent_t e0, hipEvent_t e1)
-{
-    if (cpr != chunks_per_rank(apv.Sr) || (long)mv.nranks * cpr > kMaxChunkFlags || split < 1 || split > kMaxSplit)
-        return hipErrorInvalidValue;
-    if (mv.tagged) {
-        hipExtLaunchKernelGGL((k_update_xr_p2p_tagged<false>), dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new,
-                              apv, cpr, mv, chan, epoch, x, rv, sc, parity, timeout_ticks, err, ap_src, split, stride,
-                              (double *)nullptr, (double *)nullptr);
-        return hipGetLastError();
-    }
-    hipExtLaunchKernelGGL(k_update_xr_p2p, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, cpr, mv,
-                          chan, epoch, x, rv, sc, parity, timeout_ticks, err, ap_src, split, stride);
-    return hipGetLastError();
-}
-
-hipError_t launch_chunk_exchange_selftest(int n, int rows, int row0, const double *p_like, SegView apv, int cpr,
-                                          const MailboxView &mv, int chan, unsigned long long epoch, long long timeout_ticks,
-                                          int *err, const double *ap_src, int split, long stride, double *vals, double *sums,
-                                          hipStream_t s)
-{
-    if (cpr != chunks_per_rank(apv.Sr) || (long)mv.nranks * cpr > kMaxChunkFlags || split < 1 || split > kMaxSplit)
-        return hipErrorInvalidValue;
-    if (mv.tagged) {
-        hipLaunchKernelGGL((k_update_xr_p2p_tagged<true>), dim3(update_xr_grid(n)), dim3(256), 0, s, n, rows, row0, p_like, apv, cpr, mv,
-                           chan, epoch, (double *)nullptr, SegView{}, (Scalars *)nullptr, 0, timeout_ticks, err, ap_src, split, stride,
-                           vals, sums);
-        return hipGetLastError();
-    }
-    hipLaunchKernelGGL(k_chunk_exchange_selftest, dim3(update_xr_grid(n)), dim3(256), 0, s, n, rows, row0, p_like, apv, cpr, mv,
-                       chan, epoch, timeout_ticks, err, ap_src, split, stride, vals, sums);
-    return hipGetLastError();
-}
-
-hipError_t update_xr_p2p_resident_limit(int device, bool tagged, int *workgroups)
-{
-    int per_cu = 0, cus = 0;
-    hipError_t e = tagged ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_update_xr_p2p_tagged<false>, 256, 0)
-                          : hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_update_xr_p2p, 256, 0);
-    if (e != hipSuccess) return e;
-    e = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
-    if (e != hipSuccess) return e;
-    *workgroups = per_cu * cus;
-    return hipSuccess;
-}
-
 hipError_t launch_prefold_ap(const double *parts, int split, long stride, int rows, int Sr, const double *p_loc, double *dst,
                              double *tail, const Scalars *sc, hipStream_t s)
 {
@@ -2041,15 +1494,6 @@ hipError_t launch_coo_assign(double *A, long lda, const DiaView *dv, double *dia
         hipLaunchKernelGGL((k_coo_assign<false, 1>), dim3(grid), dim3(256), 0, s, A, lda, DiaView{}, n, row0, rows, I, J, a, nz, sym, win);
         hipLaunchKernelGGL((k_coo_assign<false, 2>), dim3(grid), dim3(256), 0, s, A, lda, DiaView{}, n, row0, rows, I, J, a, nz, sym, win);
     }
-    return hipGetLastError();
-}
-
-hipError_t launch_mailbox_allgather(const MailboxView &mv, int chan, unsigned long long epoch, const double *src,
-                                    int count, int tail_off, int tail_n, double *dst, long dst_stride, int sum_off,
-                                    int copy_self, long long timeout_ticks, int *err, hipStream_t s)
-{
-    hipLaunchKernelGGL(k_mailbox_allgather, dim3(mv.nranks), dim3(256), 0, s, mv, chan, epoch, src, count, tail_off, tail_n,
-                       dst, dst_stride, sum_off, copy_self, timeout_ticks, err);
     return hipGetLastError();
 }
 

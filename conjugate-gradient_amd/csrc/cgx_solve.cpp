@@ -35,7 +35,7 @@ namespace cgxi {
 
 // ---- collectives ---------------------------------------------------------------------------------
 
-// CGX_COMM_P2P: one lean all-gather kernel over the IPC-mapped mailboxes (cgx_kernels.hip).
+// CGX_COMM_P2P: one lean all-gather kernel over the IPC-mapped mailboxes (cgx_p2p.hip).
 cgx_status p2p_allgather(cgx_ctx *ctx, int chan, const double *src, int count, double *dst, long dst_stride,
                          int copy_self, int tail_off, int tail_n, int sum_off)
 {

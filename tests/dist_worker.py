@@ -3,8 +3,8 @@
 It runs the row-block CG with the SAME exchange protocol libcgx uses (conjugate-gradient_amd/csrc/
 cgx_solve.cpp: enqueue_iteration / gather_segments), with the oracle's GEMV standing in for K1:
   * one all-gather per iteration of equal segments [Ap slice | one p.Ap partial per 512-row chunk of the slice]
-    (cgx_kernels.hip "Chunks": k_prefold_ap / the pushers of the fused P2P update); p.Ap = sum over (rank, chunk) in one
-    fixed order;
+    (cgx_kernels.hip "Chunks": k_prefold_ap / the pushers of the fused P2P update in cgx_p2p.hip); p.Ap = sum over (rank,
+    chunk) in one fixed order;
   * r and p are replicated: every rank updates all of r and reduces r.r itself, identically;
   * break: every rank must see bit-identical r.r and leave the loop at the same k.
 Rank 0 compares against the in-process oracle with the same psize and writes a JSON verdict.

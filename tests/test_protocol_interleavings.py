@@ -7,7 +7,7 @@ last exchange of the previous one -- rests on an argument about what a fast rank
 section 6; csrc/cgx_context.cpp scrub_tagged_region).  This file states the protocol as a transition system and explores all
 schedules: which rank moves next, and in which order the stores in flight arrive.
 
-Modelled (csrc/cgx_solve.cpp, csrc/cgx_context.cpp, csrc/cgx_kernels.hip):
+Modelled (csrc/cgx_solve.cpp, csrc/cgx_context.cpp, csrc/cgx_p2p.hip):
   * a rank's work is a sequence of kernels on one stream: a kernel starts when the previous one has finished, and a kernel
     finishes only when its waits are satisfied and its own stores have arrived;
   * plain all-gather (k_mailbox_allgather): per peer, payload words into the peer's slot [parity][me], then -- after they

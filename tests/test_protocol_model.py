@@ -1,4 +1,4 @@
-"""The arithmetic of the tagged-word hand-over (conjugate-gradient_amd/csrc/cgx_kernels.hip, "Tagged words"), modelled on the
+"""The arithmetic of the tagged-word hand-over (conjugate-gradient_amd/csrc/cgx_p2p.hip, "Tagged words"), modelled on the
 host: what a reader accepts and what it cannot mistake.  The kernels themselves are exercised on the GPU
 (tests/test_gpu_p2p.py); this file pins the invariants their comments claim."""
 import struct
@@ -9,7 +9,7 @@ M = 2 ** 32 - 1
 
 
 def tag_of(epoch):
-    """p2p_tag (cgx_kernels.hip, round 4): 1 + epoch mod (2^32 - 1) -- 1 ... 2^32 - 1, never 0."""
+    """p2p_tag (cgx_device.h, round 4): 1 + epoch mod (2^32 - 1) -- 1 ... 2^32 - 1, never 0."""
     return epoch % M + 1
 
 

@@ -1,5 +1,6 @@
 #!/usr/bin/env python3
-"""Print VGPR/SGPR/LDS/occupancy per kernel of csrc/cgx_kernels.hip (hipcc -Rpass-analysis)."""
+"""Print VGPR/SGPR/LDS/occupancy per kernel of csrc/cgx_kernels.hip (hipcc -Rpass-analysis).
+CGX_KERNEL_FILE=cgx_p2p.hip: the peer exchange (k_mailbox_allgather, the four instantiations of k_update_xr_p2p)."""
 import os, re, subprocess, sys
 root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 src = os.path.join(root, "conjugate-gradient_amd", "csrc", os.environ.get("CGX_KERNEL_FILE", "cgx_kernels.hip"))
