@@ -33,8 +33,11 @@ EXPORTS = [
     "cgx_probe_parse_matrix_market", "cgx_probe_p2p_mailbox_to_host", "cgx_probe_fill_matrix_hash",
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
     "cgx_solve_multi", "cgx_probe_gemv_multi",
+    "cgx_set_preconditioner", "cgx_get_preconditioner",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
+PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
+_PRECOND_NAMES = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI}
 
 
 class Config(C.Structure):
@@ -143,6 +146,8 @@ def lib():
         L.cgx_probe_resident_test.argtypes = [vp, C.c_ulonglong, C.c_int]
         L.cgx_probe_get_p2p_epoch.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
         L.cgx_solve_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
+        L.cgx_get_preconditioner.argtypes = [vp, ip]
         L.cgx_probe_gemv_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, dp]
         L.cgx_probe_parse_matrix_market.argtypes = [C.c_char_p, C.c_int, ip, ip, ip, ip, ip, ip, dp, C.c_long, C.c_char_p, C.c_int]
         for name in EXPORTS:
@@ -327,6 +332,18 @@ class CGSolver:
 
     def tolerance(self, tol):
         self._check(lib().cgx_set_tolerance(self._h, float(tol)))
+
+    def set_preconditioner(self, kind):
+        """None (plain CG) or "jacobi": takes effect at the next solve (include/cgx.h cgx_set_preconditioner)."""
+        if kind not in _PRECOND_NAMES:
+            raise ValueError("preconditioner must be None or 'jacobi', not %r" % (kind,))
+        self._check(lib().cgx_set_preconditioner(self._h, _PRECOND_NAMES[kind]))
+
+    @property
+    def preconditioner(self):
+        k = C.c_int()
+        self._check(lib().cgx_get_preconditioner(self._h, C.byref(k)))
+        return {v: n for n, v in _PRECOND_NAMES.items()}[k.value]
 
     def _size(self):
         m = C.c_int()

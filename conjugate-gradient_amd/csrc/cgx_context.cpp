@@ -90,6 +90,8 @@ void free_shard(Shard &s)
     (void)hipFree(s.ap_parts);
     (void)hipFree(s.k1_scratch);
     (void)hipFree(s.sym_parts);
+    (void)hipFree(s.dinv);
+    (void)hipFree(s.zbuf);
     (void)hipFree(s.sc);
     (void)hipFree(s.gathered);
     s = Shard{};
@@ -110,6 +112,9 @@ void free_problem(cgx_ctx *ctx)
     ctx->d_scalar_ptrs = nullptr;
     ctx->have_matrix = ctx->have_b = false;
     ctx->in_solve = false;
+    ctx->dinv_valid = false;
+    (void)hipFree(ctx->d_jbad);
+    ctx->d_jbad = nullptr;
 }
 
 // Mailbox bytes before the segment channel: flag words, chunk flag words, channel 0 (16-B slots) and channel 2 (kSlots doubles).
@@ -187,6 +192,7 @@ static int open_device_lock(int device)
 static cgx_status setup_resident(cgx_ctx *ctx, int variant)
 {
     ctx->resident = false;
+    ctx->res_parked = false;
     const bool forced = variant == 40000 || variant == 50000;
     ctx->res_forced = forced;
     if (!forced && variant != 0) return CGX_OK;
@@ -232,7 +238,10 @@ static cgx_status setup_resident(cgx_ctx *ctx, int variant)
     if (ctx->res_lock_fd < 0 && !getenv("CGX_RESIDENT_NOLOCK"))   // (the variable: diagnostics, to show what the lock is for)
         ctx->res_lock_fd = open_device_lock(ctx->device);
     ctx->rplan = pl;
-    ctx->resident = true;
+    // With a preconditioner the loop stays on the per-launch path (the persistent kernels have no Jacobi form); the plan is kept
+    // for when the preconditioner is cleared (cgx_set_preconditioner)
+    if (ctx->precond != CGX_PRECOND_NONE) ctx->res_parked = true;
+    else ctx->resident = true;
     return CGX_OK;
 }
 
@@ -430,6 +439,7 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
 
 cgx_status plan_symmetric(cgx_ctx *ctx)
 {
+    ctx->dinv_valid = false;   // behind every writer of A: the next preconditioned solve extracts the diagonal again
     if (ctx->shards.size() != 1 || ctx->nranks != 1 || ctx->banded || ctx->chunked) return CGX_OK;
     Shard &s = ctx->shards[0];
     int variant = ctx->cfg.gemv_variant;
@@ -902,6 +912,31 @@ cgx_status cgx_set_max_iter(cgx_ctx *ctx, int max_iter)
 {
     if (!ctx) return CGX_ERR_BAD_ARG;
     ctx->max_iter = max_iter;   // the reference does not validate either (cg.cc:204-216)
+    return CGX_OK;
+}
+
+cgx_status cgx_set_preconditioner(cgx_ctx *ctx, int kind)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (kind != CGX_PRECOND_NONE && kind != CGX_PRECOND_JACOBI)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner: unknown kind " + std::to_string(kind));
+    if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner: called between cgx_solve_begin and cgx_solve_end");
+    // host bookkeeping only: the diagonal is extracted (collectively) by the next cgx_solve_begin
+    ctx->precond = kind;
+    if (kind != CGX_PRECOND_NONE && ctx->resident) {
+        ctx->resident = false;
+        ctx->res_parked = true;
+    } else if (kind == CGX_PRECOND_NONE && ctx->res_parked) {
+        ctx->resident = true;
+        ctx->res_parked = false;
+    }
+    return CGX_OK;
+}
+
+cgx_status cgx_get_preconditioner(const cgx_ctx *ctx, int *kind)
+{
+    if (!ctx || !kind) return CGX_ERR_BAD_ARG;
+    *kind = ctx->precond;
     return CGX_OK;
 }
 

@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "cgx_kernels.h"
 
 namespace cgx {
@@ -233,6 +235,121 @@ __device__ __forceinline__ IterHead iteration_head(Scalars *sc, const SegView &s
     const HeadLoads hl = head_issue(sc, sv, k);
     *done = hl.done;
     return head_finish(hl, sc, sv, k, tol);
+}
+
+// ---- the Jacobi (PRECOND) form of the head ----------------------------------------------------------
+// sv is the replicated z = D^-1 r: [z (lda) | r.z partials | r.r partials], both partial sets S - Sr long, in the update
+// kernel's workgroup order.  Both sets are folded in the same fixed order as the plain head's one set: rho = r.z gives beta,
+// r.r the break; rs[] holds rho, rr[] holds r.r.  Same rule as above: all loads issued before the first wait, unconditionally.
+struct HeadLoadsPc {
+    double rsold;
+    int done;
+    double a[4];   // r.z partials
+    double b[4];   // r.r partials
+};
+
+__device__ __forceinline__ HeadLoadsPc head_issue_pc(const Scalars *sc, const SegView &sv, int k)
+{
+    HeadLoadsPc hl;
+    const int nparts = sv.S - sv.Sr, lane = threadIdx.x & 63;
+    const double *pz = sv.base + sv.Sr, *pr = sv.base + sv.S;
+    hl.done = sc->done;
+    hl.rsold = sc->rs[(k > 0 ? k - 1 : 0) & 1];
+#pragma unroll
+    for (int u = 0; u < 4; ++u) {
+        const int t = lane + 64 * u, tc = t < nparts ? t : nparts - 1;
+        const double vz = pz[tc], vr = pr[tc];
+        hl.a[u] = (t < nparts) ? vz : 0.0;
+        hl.b[u] = (t < nparts) ? vr : 0.0;
+    }
+    return hl;
+}
+
+__device__ __forceinline__ IterHead head_finish_pc(const HeadLoadsPc &hl, Scalars *sc, const SegView &sv, int k, double tol)
+{
+    IterHead h{0.0, false};
+    const int nparts = sv.S - sv.Sr, lane = threadIdx.x & 63;
+    const double *pz = sv.base + sv.Sr, *pr = sv.base + sv.S;
+    double vz = (hl.a[0] + hl.a[1]) + (hl.a[2] + hl.a[3]);
+    double vr = (hl.b[0] + hl.b[1]) + (hl.b[2] + hl.b[3]);
+    for (int t = lane + 256; t < nparts; t += 256) {                // more than 256 partials: n > 65536
+        double az[4], ar[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const bool ok = t + 64 * u < nparts;
+            az[u] = ok ? pz[t + 64 * u] : 0.0;
+            ar[u] = ok ? pr[t + 64 * u] : 0.0;
+        }
+        vz += (az[0] + az[1]) + (az[2] + az[3]);
+        vr += (ar[0] + ar[1]) + (ar[2] + ar[3]);
+    }
+    const double rznew = wave_sum(vz);                               // rho_k = r.z
+    const double rrnew = wave_sum(vr);                               // r.r: the stopping test and the report
+    const bool first = (blockIdx.x == 0 && threadIdx.x == 0) && !hl.done;
+    if (k == 0) {                                                    // p = z: beta = 0, p_old = 0
+        if (first) { sc->rs[0] = rznew; sc->rs[1] = rznew; sc->rr[0] = rrnew; sc->rr[1] = rrnew; }
+        return h;
+    }
+    if (first) { sc->rs[k & 1] = rznew; sc->rr[k & 1] = rrnew; }
+    if (sqrt(rrnew) < tol) {                                         // tol bounds the true recursive residual, as without Jacobi
+        if (first) { sc->k_final = k - 1; sc->done = 1; }
+        h.stop = true;
+        return h;
+    }
+    h.beta = rznew / hl.rsold;
+    return h;
+}
+
+// The head of either form, chosen at compile time: the K1 families take PRE as a template parameter.
+template <bool PRE>
+using HeadLoadsOf = typename std::conditional<PRE, HeadLoadsPc, HeadLoads>::type;
+
+template <bool PRE>
+__device__ __forceinline__ HeadLoadsOf<PRE> head_issue_t(const Scalars *sc, const SegView &sv, int k)
+{
+    if constexpr (PRE) return head_issue_pc(sc, sv, k);
+    else return head_issue(sc, sv, k);
+}
+
+template <bool PRE>
+__device__ __forceinline__ IterHead head_finish_t(const HeadLoadsOf<PRE> &hl, Scalars *sc, const SegView &sv, int k, double tol)
+{
+    if constexpr (PRE) return head_finish_pc(hl, sc, sv, k, tol);
+    else return head_finish(hl, sc, sv, k, tol);
+}
+
+template <bool PRE>
+__device__ __forceinline__ IterHead iteration_head_t(Scalars *sc, const SegView &sv, int k, double tol, int *done)
+{
+    const HeadLoadsOf<PRE> hl = head_issue_t<PRE>(sc, sv, k);
+    *done = hl.done;
+    return head_finish_t<PRE>(hl, sc, sv, k, tol);
+}
+
+// One row of the Jacobi update, the same function in every Jacobi update kernel (k_update_xr_pc, k_update_xr_strided_pc,
+// k_pcg_update_p2p, k_init_residual_pc), so that every transport produces the same bits: r_new = r - alpha Ap, z = dinv r_new, and the row's terms
+// of r.r and r.z.
+struct PcRow {
+    double r, z, rr, rz;
+};
+__device__ __forceinline__ PcRow pc_row(double r_new, double dinv_i)
+{
+    PcRow o;
+    o.r = r_new;
+    o.z = dinv_i * r_new;
+    o.rr = r_new * r_new;
+    o.rz = r_new * o.z;
+    return o;
+}
+__device__ __forceinline__ PcRow pc_update_row(double alpha, double ap_i, double r_i, double dinv_i)
+{
+    return pc_row(fma(-alpha, ap_i, r_i), dinv_i);
+}
+// the workgroup's two partials: r.z in z's tail, r.r behind it
+__device__ __forceinline__ void pc_store_partials(const SegView &zv, int wg, double rz, double rr)
+{
+    zv.base[zv.Sr + wg] = rz;
+    zv.base[zv.S + wg] = rr;
 }
 
 // p_new for the column pair (c, c+1); pad columns (>= n) stay exactly 0.

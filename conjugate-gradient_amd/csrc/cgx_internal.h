@@ -44,6 +44,12 @@ struct Shard {
     double *gathered = nullptr;  // kMaxRanks * kSlots doubles (DEBUG scalars of all ranks)
     cgx::GemvPlan plan{};
     cgx::SegView apv{}, rv{};
+    // Jacobi, made at the first preconditioned solve of a problem: the replicated inverse diagonal (lda
+    // doubles, zero padded) and the replicated z = D^-1 r laid out as rbuf with a second partial set behind the first
+    // ([z | r.z partials | r.r partials], cgx::SegView zv: rv's geometry)
+    double *dinv = nullptr;
+    double *zbuf = nullptr;
+    cgx::SegView zv{};
     int npartials = 0;
     double *Ap() const { return apg + (size_t)rank * apv.S; }          // this shard's Ap slice (K1 output)
     double *tail() const { return Ap() + apv.Sr; }                      // this shard's segment tail: the p.Ap partials that travel
@@ -67,6 +73,10 @@ struct cgx_ctx {
     std::vector<double> b_host;
     bool have_matrix = false, have_b = false;
     bool banded = false;         // cfg.matrix_format == CGX_MATRIX_BANDED (opt-in, not the reference's storage)
+    int precond = CGX_PRECOND_NONE;   // cgx_set_preconditioner: read by cgx_solve_begin, fixed until cgx_solve_end
+    bool dinv_valid = false;     // every shard's dinv holds the diagonal of the current matrix (checked: finite and > 0)
+    int *d_jbad = nullptr;       // device word: first row of a diagonal entry Jacobi cannot take (set-up only)
+    bool res_parked = false;     // the persistent kernel would take this problem, but the preconditioner keeps it on the per-launch path
 
     // RCCL
     const cgx::RcclApi *rccl = nullptr;

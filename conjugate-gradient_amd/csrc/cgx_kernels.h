@@ -18,6 +18,8 @@ constexpr int kMaxRanks = 64;  // gathered[] holds kMaxRanks*kSlots doubles
 // host except `done` (polled every check_every iterations).
 struct Scalars {
     double rs[2];          // rsold / rsnew ping-pong: rs[k&1] is rsold of iteration k          (cg.cc:91,116,132)
+                           // (Jacobi: rho = r.z, the numerator of alpha and beta)
+    double rr[2];          // Jacobi only: r.r in the same ping-pong, what the stopping test and the report use
     double local[kSlots];  // send buffer of the small scalar all-gather (verification phase)
     double dbg[4];
     int    done;           // set when sqrt(rsnew) < tol (cg.cc:120-121); later kernels exit at once
@@ -77,10 +79,13 @@ hipError_t launch_gemv_plain(const GemvPlan &plan, const double *A, long lda, in
 // kernel's own begin -> end as rocprofv3 sees it, with no marker packets on the stream.
 // plan.split > 1: Ap is the first of plan.split partial vectors, ap_stride doubles apart (piece s of the columns
 // writes Ap + s * ap_stride); the consumer adds them in ascending order (launch_prefold_ap, or the fused P2P update).
+// jacobi: the preconditioned form: seg is the replicated z = D^-1 r instead of r, laid out like r, with the
+// r.z partials in its tail and the r.r partials behind them (at seg.base + seg.S); the head takes beta from r.z and the break
+// from r.r.  The loop over A is the same code.
 hipError_t launch_gemv_fused(const GemvPlan &plan, const double *A, long lda, int rows, int row0,
                              const double *p_old, double *p_new, SegView seg, double *Ap, double *partials,
                              Scalars *sc, int k, double tol, hipStream_t s, hipEvent_t e_start = nullptr,
-                             hipEvent_t e_stop = nullptr, long ap_stride = 0);
+                             hipEvent_t e_stop = nullptr, long ap_stride = 0, bool jacobi = false);
 // ---- K1 for an exactly symmetric A on one GPU (plan variant 6, cgx_symv.hip) ----------------------------------------------
 // A p from the upper triangle's B x B tiles: each off-diagonal tile is read once and used twice.  The plan's fields mean:
 // R = tile edge B, U = tiles of the longest workgroup run, waves = 4, light = fold workgroups (= p.Ap partials in the tail),
@@ -99,7 +104,7 @@ hipError_t launch_symv_plain(const GemvPlan &pl, const double *A, long lda, int 
 // the fold's, so the pair spans all the work that produces Ap.
 hipError_t launch_symv_fused(const GemvPlan &pl, const double *A, long lda, int n, const double *p_old, double *p_new, SegView seg,
                              double *parts, double *Ap, double *partials, Scalars *sc, int k, double tol, hipStream_t s,
-                             hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr);
+                             hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr, bool jacobi = false);
 // *mismatch |= 1 unless A (n x n at pitch lda) equals its transpose bit for bit (64-bit words; *mismatch zeroed by the caller).
 hipError_t launch_symmetric_check(const double *A, long lda, int n, int *mismatch, hipStream_t s);
 
@@ -116,22 +121,34 @@ hipError_t launch_prefold_ap(const double *parts, int split, long stride, int ro
 // K3: p.Ap = fixed-order sum over all ranks q of the tail_count doubles at tail_off of segment q's tail;
 // alpha = rsold / max(p.Ap, rsold*1e-14); x_sub += alpha p_sub (own rows); r -= alpha Ap for ALL n rows (r is
 // replicated, rv = [r (lda) | one r.r partial per K3 workgroup]); the next K1's head folds the partials.  cg.cc:105-116.
+// dinv != nullptr: the Jacobi form -- also z = dinv * r_new into zv (the layout of rv) and, per workgroup, the r.z partial
+// into zv's tail and the r.r partial behind it (zv.base + zv.S); alpha then uses rho = r.z (sc->rs).
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s,
-                            hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr);   // optional: bound to the dispatch
+                            hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr,   // optional: bound to the dispatch
+                            const double *dinv = nullptr, SegView zv = SegView{});
 int update_xr_grid(int count);   // ceil(count/256), at most kMaxVectorGrid (above that the kernels stride over the rows)
 constexpr int kMaxVectorGrid = 1024;
 
 // Tail of the LAST executed iteration when the loop runs out (k = number of iterations done):
 // rsnew -> rs[k&1], convergence test (cg.cc:117-121,132).  One thread.
-hipError_t launch_close_iteration(Scalars *sc, SegView seg, int k, double tol, hipStream_t s);
+hipError_t launch_close_iteration(Scalars *sc, SegView seg, int k, double tol, hipStream_t s, bool jacobi = false);
 
 // K2: out[0..NV) = deterministic sum of partials (stand-alone form, setup/verification only).
 hipError_t launch_reduce_partials(const double *partials, int n, double *out, hipStream_t s);
 hipError_t launch_reduce_partials3(const double *partials, int n, double *out3, hipStream_t s);
 
 // Initial residual (cg.cc:79-85): r = b - Ap for all n rows (Ap from the gathered segments); rv tail[wg] = sum r_i^2.
-hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s);
+// dinv != nullptr (Jacobi): also z0 = dinv * r0 into zv, the r.z partials in zv's tail and the r.r partials behind them.
+hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
+                                const double *dinv = nullptr, SegView zv = SegView{});
+
+// ---- Jacobi -------------------------------------------------------------------------------------------
+// dst[i] = A(row0 + i, row0 + i) for the shard's rows (dst: its Ap slice, which the segment exchange then gathers).
+hipError_t launch_diag_slice(const double *A, long lda, int rows, int row0, double *dst, hipStream_t s);
+// From the gathered slices: dinv[c] = 1 / a_cc for c < n, 0 up to lda; *bad = min(*bad, first row whose a_cc is not finite and
+// > 0) (the caller sets *bad = INT_MAX before).
+hipError_t launch_jacobi_dinv(SegView apv, int n, long lda, double *dinv, int *bad, hipStream_t s);
 
 // v_full[c] = segment value of column c (c < n), 0 for the pad: turns gathered slices into a replicated vector.
 hipError_t launch_unpack_segments(SegView seg, double *v_full, long lda, hipStream_t s);
@@ -254,7 +271,7 @@ hipError_t launch_update_xr_p2p(int n, int rows, int row0, const double *p_new, 
                                 const MailboxView &mv, int chan, unsigned long long epoch, double *x, SegView rv, Scalars *sc,
                                 int parity, long long timeout_ticks, int *err, hipStream_t s,
                                 const double *ap_src, int split, long stride, hipEvent_t e_start = nullptr,
-                                hipEvent_t e_stop = nullptr);
+                                hipEvent_t e_stop = nullptr, const double *dinv = nullptr, SegView zv = SegView{});
 // The exchange of launch_update_xr_p2p alone (the same kernel template, SELFTEST = true), on caller data: vals[i] = the Ap
 // element read for global row i (n doubles), sums[wg] = the folded chunk partials as workgroup wg saw them
 // (update_xr_grid(n) doubles).

@@ -37,7 +37,9 @@
 
 namespace cgx {
 
-enum { kPlain = 0, kFusedSingle = 1 };   // the fused form always reads the replicated, contiguous r
+// the fused form always reads the replicated, contiguous r -- or, Jacobi, the replicated z laid out
+// exactly like it: the same loop with another source pointer, and the PRECOND form of the head
+enum { kPlain = 0, kFusedSingle = 1, kFusedJacobi = 2 };
 
 // load_a, the exchanged residual (seg_*), the iteration head and make_p live in cgx_device.h (shared with cgx_symv.hip).
 
@@ -71,6 +73,7 @@ __global__ __launch_bounds__(WAVES * 64, (LIGHT ? 2 : ((R == 8 && U == 2) ? 4 : 
                                                                Scalars *sc, int k, double tol, int split, long ap_stride)
 {
     constexpr bool FUSED = MODE != kPlain;
+    constexpr bool PRE = MODE == kFusedJacobi;   // sv is z, not r: p = z + beta p_old; the head folds r.z and r.r
     constexpr bool NT = true;   // A is streamed once: non-temporal loads keep p and r in L2 (+12 % measured)
     __shared__ double red[WAVES][R];
 
@@ -180,8 +183,8 @@ __global__ __launch_bounds__(WAVES * 64, (LIGHT ? 2 : ((R == 8 && U == 2) ? 4 : 
         // live registers push the 4-per-CU kernel past 128 VGPRs: the 4096-workgroup grid of N=32768 then runs 5.33
         // rounds instead of 4, -1.2 %) and for the one-round form, which has 256 registers.
         constexpr bool HOIST = LIGHT || R * U <= 8;
-        HeadLoads hl{};
-        if constexpr (FUSED) hl = head_issue(sc, sv, k);
+        HeadLoadsOf<PRE> hl{};
+        if constexpr (FUSED) hl = head_issue_t<PRE>(sc, sv, k);
         if constexpr (LIGHT && PART) {
             long er = row0 + (lane & (R - 1));
             if (er > rows - 1) er = rows - 1;
@@ -194,7 +197,7 @@ __global__ __launch_bounds__(WAVES * 64, (LIGHT ? 2 : ((R == 8 && U == 2) ? 4 : 
         const bool first = HOIST && full(c);
         if (first) load_trip(pv, rv2, av, c);
         if constexpr (FUSED) {
-            const IterHead h = head_finish(hl, sc, sv, k, tol);
+            const IterHead h = head_finish_t<PRE>(hl, sc, sv, k, tol);
             if (hl.done || h.stop) return;
             beta = h.beta;
         }
@@ -283,12 +286,13 @@ __global__ __launch_bounds__(WAVES * 64) void k_gemv_ldsp(const double *__restri
                                                            Scalars *sc, int k, double tol)
 {
     constexpr bool FUSED = MODE != kPlain;
-    constexpr bool SINGLE = MODE == kFusedSingle;
+    constexpr bool SINGLE = MODE == kFusedSingle || MODE == kFusedJacobi;
+    constexpr bool PRE = MODE == kFusedJacobi;
     constexpr bool NT = true;
     double beta = 0.0;
     if constexpr (FUSED) {
         int done;
-        const IterHead h = iteration_head(sc, sv, k, tol, &done);
+        const IterHead h = iteration_head_t<PRE>(sc, sv, k, tol, &done);
         if (done || h.stop) return;
         beta = h.beta;
     }
@@ -499,12 +503,71 @@ __global__ __launch_bounds__(256) void k_update_xr(int n, int rows, int row0, co
     if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;   // one r.r partial per workgroup, folded by the next K1's head
 }
 
+// K3, Jacobi form: k_update_xr with alpha = rho / p.Ap (rho = r.z in sc->rs) and, per row, z = dinv r_new (pc_update_row);
+// dinv[i] is loaded with the other loads ahead of the first wait.  zv: the replicated z, laid out as rv; the workgroup's r.z
+// partial goes into its tail, the r.r partial behind that (pc_store_partials), in the same order as the plain r.r partials.
+__global__ __launch_bounds__(256) void k_update_xr_pc(int n, int rows, int row0, const double *__restrict__ p_new, SegView apv,
+                                                       int tail_off, int tail_count, double *__restrict__ x, SegView rv, Scalars *sc,
+                                                       int parity, const double *__restrict__ dinv, SegView zv)
+{
+    __shared__ double lds[4];
+    double *r = rv.base;
+    const int done = sc->done;
+    const double rsold = sc->rs[parity];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int li = i - row0;
+    const bool in = i < n, own = in && li >= 0 && li < rows;
+    double ap_i = 0.0, r_i = 0.0, d_i = 0.0, p_i = 0.0, x_i = 0.0;
+    if (in) { ap_i = seg_load(apv, i); r_i = r[i]; d_i = dinv[i]; }
+    if (own) { p_i = p_new[i]; x_i = x[li]; }
+    double cs = 0.0;
+    {
+        const int total = apv.nranks * tail_count;
+        const double *tails = apv.base + apv.Sr + tail_off;
+        auto at = [&](int f) {
+            if (apv.nranks == 1) return tails[f];
+            const int q = f / tail_count;
+            return tails[(long)q * apv.S + (f - q * tail_count)];
+        };
+        for (int f = threadIdx.x; f < total; f += 4 * 256) {   // the plain kernel's order
+            double a[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int g = f + u * 256;
+                const double val = at(g < total ? g : total - 1);
+                a[u] = g < total ? val : 0.0;
+            }
+            cs += (a[0] + a[1]) + (a[2] + a[3]);
+        }
+    }
+    if (done) return;
+    const double conj = block_sum<4>(cs, lds);
+    const double alpha = safeguarded_alpha(rsold, conj);             // alpha = rho / p.Ap, the bound relative to rho
+    double rr = 0.0, rz = 0.0;
+    if (in) {
+        const PcRow o = pc_update_row(alpha, ap_i, r_i, d_i);
+        r[i] = o.r;
+        zv.base[i] = o.z;
+        rr = o.rr;
+        rz = o.rz;
+    }
+    if (own) x[li] = fma(alpha, p_i, x_i);
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+}
+
 // Loop ran out after k iterations: the tail of iteration k-1 that the next K1 would have done (same code,
 // same bits), or, for k == 0, the rsold of cg.cc:91-92.
 __global__ __launch_bounds__(256) void k_close_iteration(Scalars *sc, SegView sv, int k, double tol)
 {
     int done;
     (void)iteration_head(sc, sv, k, tol, &done);
+}
+__global__ __launch_bounds__(256) void k_close_iteration_pc(Scalars *sc, SegView zv, int k, double tol)
+{
+    int done;
+    (void)iteration_head_t<true>(sc, zv, k, tol, &done);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -539,6 +602,45 @@ __global__ __launch_bounds__(256) void k_init_residual(int n, const double *__re
     }
     rr = block_sum<4>(rr, lds);
     if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;   // same slots as K3's partials: K1(0) folds them (cg.cc:91-92)
+}
+
+// Jacobi set-up: r0 = b - A x0 as k_init_residual, z0 = dinv r0, the r.z / r.r partials into zv (k_update_xr_pc's slots).
+__global__ __launch_bounds__(256) void k_init_residual_pc(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
+                                                           const double *__restrict__ dinv, SegView zv)
+{
+    __shared__ double lds[4];
+    double *r = rv.base;
+    double rr = 0.0, rz = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const PcRow o = pc_row(b_full[i] - seg_load(apv, (int)i), dinv[i]);
+        r[i] = o.r;
+        zv.base[i] = o.z;
+        rr += o.rr;
+        rz += o.rz;
+    }
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+}
+
+// Jacobi set-up, once per problem: the diagonal of the shard's rows into its Ap slice (then gathered like Ap) ...
+__global__ __launch_bounds__(256) void k_diag_slice(const double *__restrict__ A, long lda, int rows, int row0, double *__restrict__ dst)
+{
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long)gridDim.x * 256) dst[i] = A[i * lda + row0 + i];
+}
+
+// ... and from the gathered slices the replicated inverse, zero padded; *bad = the first row whose entry is not finite and > 0
+__global__ __launch_bounds__(256) void k_jacobi_dinv(SegView apv, int n, long lda, double *__restrict__ dinv, int *bad)
+{
+    for (long c = (long)blockIdx.x * 256 + threadIdx.x; c < lda; c += (long)gridDim.x * 256) {
+        double v = 0.0;
+        if (c < n) {
+            const double d = seg_load(apv, (int)c);
+            if (!(d > 0.0 && d <= 1.7976931348623157e308)) atomicMin(bad, (int)c);   // NaN, <= 0, +inf
+            v = 1.0 / d;
+        }
+        dinv[c] = v;
+    }
 }
 
 // dst[0..count) = src[0..count); either side may be pinned host memory (x0 in / x out of a solve: a kernel instead of
@@ -731,6 +833,39 @@ __global__ __launch_bounds__(256) void k_update_xr_strided(int n, int rows, int 
     }
     rr = block_sum<4>(rr, lds);
     if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;
+}
+
+// The Jacobi form of k_update_xr_strided (more than 256 * kMaxVectorGrid rows).
+__global__ __launch_bounds__(256) void k_update_xr_strided_pc(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
+                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ dinv,
+                                                               SegView zv)
+{
+    __shared__ double lds[4];
+    double *r = rv.base;
+    const int done = sc->done;
+    const double rsold = sc->rs[parity];
+    double cs = 0.0;
+    for (int q = 0; q < apv.nranks; ++q) {
+        const double *tail = apv.base + (long)q * apv.S + apv.Sr + tail_off;
+        for (int j = threadIdx.x; j < tail_count; j += 256) cs += tail[j];
+    }
+    if (done) return;
+    const double conj = block_sum<4>(cs, lds);
+    const double alpha = safeguarded_alpha(rsold, conj);
+    double rr = 0.0, rz = 0.0;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
+        const PcRow o = pc_update_row(alpha, seg_load(apv, (int)i), r[i], dinv[i]);
+        r[i] = o.r;
+        zv.base[i] = o.z;
+        rr += o.rr;
+        rz += o.rz;
+        const long li = i - row0;
+        if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);
+    }
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1200,13 +1335,13 @@ hipError_t launch_gemv_plain(const GemvPlan &pl, const double *A, long lda, int 
 
 hipError_t launch_gemv_fused(const GemvPlan &pl, const double *A, long lda, int rows, int row0, const double *p_old,
                              double *p_new, SegView seg, double *Ap, double *partials, Scalars *sc, int k, double tol,
-                             hipStream_t s, hipEvent_t e_start, hipEvent_t e_stop, long ap_stride)
+                             hipStream_t s, hipEvent_t e_start, hipEvent_t e_stop, long ap_stride, bool jacobi)
 {
     GemvArgs g{A, lda, rows, row0, p_old, p_new, seg, Ap, partials, sc, k, tol, e_start, e_stop};
     g.split = pl.split;
     g.ap_stride = ap_stride;
     if (pl.split > 1 && (!pl.light || ap_stride <= 0)) return hipErrorInvalidValue;
-    return dispatch_gemv<kFusedSingle>(pl, g, s);
+    return jacobi ? dispatch_gemv<kFusedJacobi>(pl, g, s) : dispatch_gemv<kFusedSingle>(pl, g, s);
 }
 
 int update_xr_grid(int count)
@@ -1217,8 +1352,17 @@ int update_xr_grid(int count)
 
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s, hipEvent_t e0,
-                            hipEvent_t e1)
+                            hipEvent_t e1, const double *dinv, SegView zv)
 {
+    if (dinv) {
+        if ((long)update_xr_grid(n) * 256 >= n)
+            hipExtLaunchKernelGGL(k_update_xr_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,
+                                  tail_off, tail_count, x, rv, sc, parity, dinv, zv);
+        else
+            hipExtLaunchKernelGGL(k_update_xr_strided_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new,
+                                  apv, tail_off, tail_count, x, rv, sc, parity, dinv, zv);
+        return hipGetLastError();
+    }
     if ((long)update_xr_grid(n) * 256 >= n)   // one row per thread: every dense problem
         hipExtLaunchKernelGGL(k_update_xr, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, tail_off,
                               tail_count, x, rv, sc, parity, partials);
@@ -1399,9 +1543,10 @@ hipError_t launch_prefold_ap(const double *parts, int split, long stride, int ro
     return hipGetLastError();
 }
 
-hipError_t launch_close_iteration(Scalars *sc, SegView seg, int k, double tol, hipStream_t s)
+hipError_t launch_close_iteration(Scalars *sc, SegView seg, int k, double tol, hipStream_t s, bool jacobi)
 {
-    hipLaunchKernelGGL(k_close_iteration, dim3(1), dim3(256), 0, s, sc, seg, k, tol);
+    if (jacobi) hipLaunchKernelGGL(k_close_iteration_pc, dim3(1), dim3(256), 0, s, sc, seg, k, tol);
+    else hipLaunchKernelGGL(k_close_iteration, dim3(1), dim3(256), 0, s, sc, seg, k, tol);
     return hipGetLastError();
 }
 
@@ -1430,9 +1575,24 @@ hipError_t launch_solve_end(int n, const double *Ax, const double *b, const doub
     return hipGetLastError();
 }
 
-hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s)
+hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
+                                const double *dinv, SegView zv)
 {
-    hipLaunchKernelGGL(k_init_residual, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, partials);
+    if (dinv) hipLaunchKernelGGL(k_init_residual_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, dinv, zv);
+    else hipLaunchKernelGGL(k_init_residual, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, partials);
+    return hipGetLastError();
+}
+
+hipError_t launch_diag_slice(const double *A, long lda, int rows, int row0, double *dst, hipStream_t s)
+{
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_diag_slice, dim3(update_xr_grid(rows)), dim3(256), 0, s, A, lda, rows, row0, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_jacobi_dinv(SegView apv, int n, long lda, double *dinv, int *bad, hipStream_t s)
+{
+    hipLaunchKernelGGL(k_jacobi_dinv, dim3(update_xr_grid((int)lda)), dim3(256), 0, s, apv, n, lda, dinv, bad);
     return hipGetLastError();
 }
 

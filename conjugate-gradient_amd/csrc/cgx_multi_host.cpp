@@ -155,6 +155,8 @@ extern "C" {
 cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
 {
     CGX_TRY(check_multi(ctx, "cgx_solve_multi", nrhs, B, ldb, X, ldx));
+    if (ctx->precond != CGX_PRECOND_NONE)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_solve_multi: no preconditioner for several right-hand sides (cgx_set_preconditioner)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     MultiView v;
     CGX_TRY(ensure_multi(ctx, &v));

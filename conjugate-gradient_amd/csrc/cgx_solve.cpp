@@ -17,6 +17,7 @@
 #include <sys/file.h>
 
 #include <cerrno>
+#include <climits>
 #include <thread>
 
 #include <algorithm>
@@ -106,6 +107,50 @@ cgx_status gather_segments(cgx_ctx *ctx, bool with_tail)
 
 namespace cgxi {
 
+// ---- Jacobi set-up -----------------------------------------------------------
+// Collective, inside cgx_solve_begin: the refusals, the buffers, and -- once per matrix -- the diagonal.  Every shard reads the
+// diagonal of its own rows into its Ap slice, the transport's segment exchange gathers the slices, and every shard forms the
+// replicated dinv from its gathered copy.  The check (finite and > 0) runs on that copy, so all ranks take the same decision,
+// and only after the exchange, so no rank is left waiting in it.
+cgx_status prepare_jacobi(cgx_ctx *ctx)
+{
+    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, "Jacobi preconditioner: banded storage is not supported");
+    if (ctx->res_forced)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, "Jacobi preconditioner: the persistent kernels (gemv_variant 40000 / 50000) have no Jacobi form");
+    hipStream_t st = ctx->stream;
+    for (auto &s : ctx->shards) {
+        if (!s.dinv) {
+            const size_t zbytes = (size_t)(s.rv.S + (s.rv.S - s.rv.Sr)) * sizeof(double);
+            HIP_TRY(ctx, hipMalloc(&s.dinv, (size_t)ctx->lda * sizeof(double)));
+            HIP_TRY(ctx, hipMalloc(&s.zbuf, zbytes));
+            HIP_TRY(ctx, hipMemsetAsync(s.zbuf, 0, zbytes, st));
+        }
+        s.zv = s.rv;
+        s.zv.base = s.zbuf;
+    }
+    if (ctx->dinv_valid) return CGX_OK;
+    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_diag_slice(s.A, ctx->lda, s.rows, s.row0, s.Ap(), st));
+    CGX_TRY(gather_segments(ctx, false));
+    if (!ctx->d_jbad) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_jbad), sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_jbad, 0x7f, sizeof(int), st));   // 0x7f7f7f7f: above every row index
+    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_jacobi_dinv(s.apv, ctx->n, ctx->lda, s.dinv, ctx->d_jbad, st));
+    int bad = INT_MAX;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, ctx->d_jbad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (bad >= 0 && bad < ctx->n) {
+        const Shard &s = ctx->shards[0];
+        const int nl = s.apv.n_loc, P = s.apv.nranks;
+        const int q = nl > 0 ? std::min(bad / nl, P - 1) : P - 1;
+        double v = 0.0;
+        HIP_TRY(ctx, hipMemcpy(&v, s.apg + bad + (long)q * s.apv.seg_gap, sizeof(double), hipMemcpyDeviceToHost));
+        char msg[160];
+        snprintf(msg, sizeof msg, "Jacobi preconditioner: diagonal entry of row %d is %.17g (every entry must be finite and > 0)", bad, v);
+        return fail(ctx, CGX_ERR_BAD_ARG, msg);
+    }
+    ctx->dinv_valid = true;
+    return CGX_OK;
+}
+
 // ---- K1 with optional event bracketing -----------------------------------------------------------
 cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)
 {
@@ -186,17 +231,18 @@ cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
         }
     }
     hipEvent_t m1 = (timed && ctx->cfg.profile_markers) ? ctx->ev_pool[ctx->ev_used - 1] : nullptr;
+    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;   // p = z + beta p_old: K1 reads z where it reads r otherwise
     if (ctx->banded)
         HIP_TRY(ctx, cgx::launch_spmv_dia_fused(s.plan, s.dia, s.rows, s.row0, ctx->n, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1],
                                                 s.rv, s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1));
     else if (s.plan.variant == 6)   // the event pair spans the tile kernel and the fold: all the work that produces Ap
-        HIP_TRY(ctx, cgx::launch_symv_fused(s.plan, s.A, ctx->lda, ctx->n, s.p[k & 1], s.p[(k + 1) & 1], s.rv, s.sym_parts, s.Ap(),
-                                            s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1));
+        HIP_TRY(ctx, cgx::launch_symv_fused(s.plan, s.A, ctx->lda, ctx->n, s.p[k & 1], s.p[(k + 1) & 1], pc ? s.zv : s.rv, s.sym_parts,
+                                            s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1, pc));
     else
-        HIP_TRY(ctx, cgx::launch_gemv_fused(s.plan, s.A, ctx->lda, s.rows, s.row0, s.p[k & 1], s.p[(k + 1) & 1], s.rv,
+        HIP_TRY(ctx, cgx::launch_gemv_fused(s.plan, s.A, ctx->lda, s.rows, s.row0, s.p[k & 1], s.p[(k + 1) & 1], pc ? s.zv : s.rv,
                                             s.plan.split > 1 ? s.ap_parts : s.Ap(),
                                             (ctx->chunked && s.plan.light) ? nullptr : s.k1_part(),   // chunked: nobody folds K1's own partials
-                                            s.sc, k, ctx->tol, ctx->stream, e0, e1, ctx->seg_Sr));
+                                            s.sc, k, ctx->tol, ctx->stream, e0, e1, ctx->seg_Sr, pc));
     if (m1) HIP_TRY(ctx, hipEventRecord(m1, ctx->stream));
     return CGX_OK;
 }
@@ -247,6 +293,7 @@ cgx_status harvest_gemv_events(cgx_ctx *ctx)
 cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
 {
     hipStream_t st = ctx->stream;
+    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
     // tail of iteration k-1 (cg.cc:117-132) + GEMV and p.Ap partials of iteration k (cg.cc:100-105)
     for (auto &s : ctx->shards) CGX_TRY(run_gemv_fused(ctx, s, k));
     if (ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange) {
@@ -258,7 +305,8 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
         CGX_TRY(take_update_events(ctx, &u0, &u1));
         HIP_TRY(ctx, cgx::launch_update_xr_p2p(ctx->n, s.rows, s.row0, s.p[(k + 1) & 1], s.apv, ctx->npart, ctx->mv, 1, epoch,
                                                s.x, s.rv, s.sc, k & 1, ctx->p2p_timeout_ticks, ctx->d_p2p_err, st,
-                                               s.plan.split > 1 ? s.ap_parts : s.Ap(), s.plan.split, ctx->seg_Sr, u0, u1));
+                                               s.plan.split > 1 ? s.ap_parts : s.Ap(), s.plan.split, ctx->seg_Sr, u0, u1,
+                                               pc ? s.dinv : nullptr, s.zv));
         return CGX_OK;
     }
     // every other multi-rank consumer: K1's column pieces added up into the Ap slice of the segment, one p.Ap partial per
@@ -275,7 +323,8 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
         // (variant 6: the fold's partials, fewer than the tail holds)
         const int count = folded ? 1 : (s.plan.variant == 6 ? cgx::plan_partials(s.plan) : ctx->npart);
         HIP_TRY(ctx, cgx::launch_update_xr(ctx->n, s.rows, s.row0, s.p[(k + 1) & 1], s.apv, folded ? ctx->npart : 0,
-                                           count, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1));   // cg.cc:105-116
+                                           count, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1,   // cg.cc:105-116
+                                           pc ? s.dinv : nullptr, s.zv));
     }
     return CGX_OK;
 }
@@ -509,6 +558,8 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
     if (!ctx || !x0) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_solve_begin: bad argument");
     if (!ctx->have_matrix || !ctx->have_b) return fail(ctx, CGX_ERR_BAD_ARG, "matrix and source term must be set before solve");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
+    if (pc) CGX_TRY(prepare_jacobi(ctx));
     ctx->t_begin = wall_now();
     ctx->t_loop = 0;
     ctx->k = 0;
@@ -554,9 +605,10 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
     for (auto &s : ctx->shards) CGX_TRY(run_gemv_plain(ctx, s, s.p[0]));                             // cg.cc:79-81
     CGX_TRY(gather_segments(ctx, false));
     for (auto &s : ctx->shards)
-        HIP_TRY(ctx, cgx::launch_init_residual(n, s.b_full, s.apv, s.rv, s.partials, st));           // cg.cc:82
+        HIP_TRY(ctx, cgx::launch_init_residual(n, s.b_full, s.apv, s.rv, s.partials, st,            // cg.cc:82 (Jacobi: and z0)
+                                               pc ? s.dinv : nullptr, s.zv));
     for (auto &s : ctx->shards) {
-        // p_old of iteration 0 is 0, so K1(0) forms p = r + 0*0 = r  (p_sub = r_sub, cg.cc:85)
+        // p_old of iteration 0 is 0, so K1(0) forms p = r + 0*0 = r  (p_sub = r_sub, cg.cc:85; Jacobi: p0 = z0)
         HIP_TRY(ctx, hipMemsetAsync(s.p[0], 0, vec_bytes, st));
         HIP_TRY(ctx, hipMemsetAsync(s.p[1], 0, vec_bytes, st));
     }
@@ -631,8 +683,9 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
     // The convergence test of the last enqueued iteration is normally done by the NEXT K1; when the loop
     // ran out there is none, so close it here (cg.cc:117-121,132).
     // (the LDS-resident kernel has made that test itself; with no iteration done the state is the per-launch path's)
+    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
     if (!ctx->resident || ctx->k == 0) {
-        for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_close_iteration(s.sc, s.rv, ctx->k, ctx->tol, st));
+        for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_close_iteration(s.sc, pc ? s.zv : s.rv, ctx->k, ctx->tol, st, pc));
         CGX_TRY(read_flags_sync(ctx));
     }   // (resident: done / k_final were read behind the last launch, resident_steps; one host synchronisation less)
     const int k_exit = ctx->done ? ctx->k_final : ctx->k;
@@ -706,8 +759,9 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
         memset(res, 0, sizeof *res);
         res->iterations = k_exit;
         res->converged = ctx->done ? 1 : 0;
-        res->residual_prev = std::sqrt(hs.rs[k_exit & 1]);         // sqrt(rsold) as printed, cg.cc:152-153
-        res->residual_last = std::sqrt(hs.rs[(k_exit + 1) & 1]);
+        const double *rr = pc ? hs.rr : hs.rs;                       // Jacobi: rs[] holds r.z, rr[] r.r
+        res->residual_prev = std::sqrt(rr[k_exit & 1]);             // sqrt(rsold) as printed, cg.cc:152-153
+        res->residual_last = std::sqrt(rr[(k_exit + 1) & 1]);
         if (!ctx->done) res->residual_last = res->residual_prev;    // loop ran out: rsold == rsnew (cg.cc:132)
         res->x_norm = std::sqrt(sums[2]);
         res->rel_residual = std::sqrt(sums[0]) / std::sqrt(sums[1]);

@@ -45,116 +45,26 @@ __device__ __forceinline__ void tri_tile(long t, long nb, long *I, long *J)
 //     broadcast from the lane that holds it (v_readlane), the 4 waves combined in LDS in wave order.
 // One barrier per tile; LDS is double buffered by tile parity, so the next tile's writes never meet this tile's reads.
 // FUSED: the iteration head first (every wave, as K1: no barrier in front of it), p = r + beta p_old in registers.
+// k_pcg_symv_tiles (Jacobi): the same body (cgx_symv_tiles.inc) with PRE = true -- sv is the replicated z
+// instead of r, which vec2 / vec1 read through the same pointer, and the head is the PRECOND form (beta from r.z, the break from r.r).
 template <int B, bool FUSED>
 __global__ __launch_bounds__(256, 4) void k_symv_tiles(const double *__restrict__ A, long lda, int n, int ncols, int nb, long tiles,
                                                        const double *__restrict__ v, double *__restrict__ p_new, SegView sv,
                                                        double *__restrict__ parts, Scalars *sc, int k, double tol)
 {
-    constexpr int H = B / 128;     // 1-KiB column pieces per row of a tile
-    constexpr int R = 16 / H;      // rows per batch
-    constexpr int RW = B / 4;      // rows per wave per tile
-    static_assert(H >= 1 && RW % R == 0 && RW <= 64, "tile shape");
-    __shared__ double rowbuf[2][B];
-    __shared__ double colbuf[2][4][B];
+    constexpr bool PRE = false;
+#include "cgx_symv_tiles.inc"
+}
 
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    const long G = gridDim.x;
-    const long t0 = tiles * (long)blockIdx.x / G, t1 = tiles * ((long)blockIdx.x + 1) / G;
-    double beta = 0.0;
-    if constexpr (FUSED) {
-        const HeadLoads hl = head_issue(sc, sv, k);
-        const IterHead h = head_finish(hl, sc, sv, k, tol);
-        if (hl.done || h.stop) return;   // uniform over the grid: nothing is stored
-        beta = h.beta;
-    }
-    if (t0 >= t1) return;
-    long I, J;
-    tri_tile(t0, nb, &I, &J);
-    const double *rfull = sv.base;   // FUSED: the replicated r, contiguous and zero padded up to lda
-
-    // the vector at the column pair (c, c+1) / at row i; exactly 0 from ncols / n on (and never read there)
-    auto vec2 = [&](int c) {
-        const bool ok = c < ncols;
-        const int cc = ok ? c : 0;
-        d2 p = *reinterpret_cast<const d2 *>(v + cc);
-        if constexpr (FUSED) {
-            const d2 r = *reinterpret_cast<const d2 *>(rfull + cc);
-            p.x = fma(beta, p.x, r.x);                                   // cg.cc:127-129, the bits K1 stores
-            p.y = fma(beta, p.y, r.y);
-        }
-        p.x = ok ? p.x : 0.0;
-        p.y = ok ? p.y : 0.0;
-        return p;
-    };
-    auto vec1 = [&](int i) {
-        const bool ok = i < n;
-        const int ii = ok ? i : 0;
-        double p = v[ii];
-        if constexpr (FUSED) p = fma(beta, p, rfull[ii]);
-        return ok ? p : 0.0;
-    };
-
-    int buf = 0;
-    for (long t = t0; t < t1; ++t) {
-        const int r0 = (int)(I * B), c0 = (int)(J * B);
-        const bool diag = I == J;
-        int col[H];
-        d2 pj[H];
-#pragma unroll
-        for (int h = 0; h < H; ++h) {
-            col[h] = c0 + h * 128 + 2 * lane;
-            pj[h] = vec2(col[h]);
-            if constexpr (FUSED)   // p_new of block J is stored once: by wave 0 of the diagonal tile
-                if (diag && w == 0 && col[h] < ncols) *reinterpret_cast<d2 *>(p_new + col[h]) = pj[h];
-            if (col[h] >= ncols) col[h] = ncols - 2;   // clamped address; pj = 0 there and the column is never stored
-        }
-        const double pi_l = vec1(r0 + w * RW + (lane & (RW - 1)));   // p of the wave's row (lane & (RW-1)), 0 from n on
-        d2 cacc[H];
-#pragma unroll
-        for (int h = 0; h < H; ++h) cacc[h] = d2{0.0, 0.0};
-
-        for (int b = 0; b < RW / R; ++b) {
-            const int rb = r0 + w * RW + b * R;
-            d2 a[R][H];
-#pragma unroll
-            for (int q = 0; q < R; ++q) {
-                long row = rb + q;
-                if (row > n - 1) row = n - 1;   // rows from n on: the last row again, with p = 0 and no row store
-                const char *ar = reinterpret_cast<const char *>(A + row * lda);
-#pragma unroll
-                for (int h = 0; h < H; ++h) a[q][h] = load_a<true>(reinterpret_cast<const double *>(ar + (unsigned)col[h] * 8u));
-            }
-            __builtin_amdgcn_sched_barrier(0);   // all of the batch's loads in flight before the first FMA
-            double racc[R];
-#pragma unroll
-            for (int q = 0; q < R; ++q) {
-                racc[q] = fma(a[q][0].y, pj[0].y, a[q][0].x * pj[0].x);
-#pragma unroll
-                for (int h = 1; h < H; ++h) racc[q] = fma(a[q][h].y, pj[h].y, fma(a[q][h].x, pj[h].x, racc[q]));
-                const int src = b * R + q;   // wave-uniform
-                const double pr = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(pi_l), src),
-                                                   __builtin_amdgcn_readlane(__double2loint(pi_l), src));
-#pragma unroll
-                for (int h = 0; h < H; ++h) {
-                    cacc[h].x = fma(a[q][h].x, pr, cacc[h].x);
-                    cacc[h].y = fma(a[q][h].y, pr, cacc[h].y);
-                }
-            }
-            const int myrow = wave_sum_rows<R>(racc, lane);
-            if ((lane & (64 / R - 1)) == 0) rowbuf[buf][w * RW + b * R + myrow] = racc[0];
-        }
-        if (!diag)
-#pragma unroll
-            for (int h = 0; h < H; ++h) *reinterpret_cast<d2 *>(&colbuf[buf][w][h * 128 + 2 * lane]) = cacc[h];
-        __syncthreads();
-        for (int e = threadIdx.x; e < B; e += 256) {
-            if (r0 + e < n) parts[J * lda + r0 + e] = rowbuf[buf][e];                                    // slot J of block I
-            if (!diag && c0 + e < n)
-                parts[I * lda + c0 + e] = ((colbuf[buf][0][e] + colbuf[buf][1][e]) + colbuf[buf][2][e]) + colbuf[buf][3][e];   // slot I of block J
-        }
-        buf ^= 1;
-        if (++J == nb) { ++I; J = I; }
-    }
+// The Jacobi form (fused only): sv is the replicated z; the PRECOND head
+template <int B>
+__global__ __launch_bounds__(256, 4) void k_pcg_symv_tiles(const double *__restrict__ A, long lda, int n, int ncols, int nb, long tiles,
+                                                       const double *__restrict__ v, double *__restrict__ p_new, SegView sv,
+                                                       double *__restrict__ parts, Scalars *sc, int k, double tol)
+{
+    constexpr bool FUSED = true;
+    constexpr bool PRE = true;
+#include "cgx_symv_tiles.inc"
 }
 
 // Ap[i] = the nb slots of row i, i < Sr; tail[wg] = the workgroup's part of p . Ap (cg.cc:105).  A workgroup owns 128 rows (a
@@ -258,15 +168,19 @@ GemvPlan plan_symv(int n, long lda, int cus)
 
 namespace {
 
-template <bool FUSED>
+template <bool FUSED, bool PRE = false>
 hipError_t launch_symv(const GemvPlan &pl, const double *A, long lda, int n, const double *v, double *p_new, SegView sv,
                        double *parts, double *Ap, double *tail, Scalars *sc, int k, double tol, hipStream_t s, hipEvent_t e0,
                        hipEvent_t e1)
 {
     if (pl.variant != 6 || pl.R != kSymvTile || n < 2) return hipErrorInvalidValue;
     const long tiles = (long)pl.split * (pl.split + 1) / 2;
-    hipExtLaunchKernelGGL((k_symv_tiles<kSymvTile, FUSED>), dim3(pl.grid), dim3(256), 0, s, e0, nullptr, 0, A, lda, n, pl.ncols,
-                          pl.split, tiles, v, p_new, sv, parts, sc, k, tol);
+    if constexpr (PRE)
+        hipExtLaunchKernelGGL((k_pcg_symv_tiles<kSymvTile>), dim3(pl.grid), dim3(256), 0, s, e0, nullptr, 0, A, lda, n, pl.ncols,
+                              pl.split, tiles, v, p_new, sv, parts, sc, k, tol);
+    else
+        hipExtLaunchKernelGGL((k_symv_tiles<kSymvTile, FUSED>), dim3(pl.grid), dim3(256), 0, s, e0, nullptr, 0, A, lda, n, pl.ncols,
+                              pl.split, tiles, v, p_new, sv, parts, sc, k, tol);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const int Sr = (n + 1) / 2 * 2;
@@ -285,8 +199,9 @@ hipError_t launch_symv_plain(const GemvPlan &pl, const double *A, long lda, int 
 
 hipError_t launch_symv_fused(const GemvPlan &pl, const double *A, long lda, int n, const double *p_old, double *p_new, SegView seg,
                              double *parts, double *Ap, double *partials, Scalars *sc, int k, double tol, hipStream_t s,
-                             hipEvent_t e_start, hipEvent_t e_stop)
+                             hipEvent_t e_start, hipEvent_t e_stop, bool jacobi)
 {
+    if (jacobi) return launch_symv<true, true>(pl, A, lda, n, p_old, p_new, seg, parts, Ap, partials, sc, k, tol, s, e_start, e_stop);
     return launch_symv<true>(pl, A, lda, n, p_old, p_new, seg, parts, Ap, partials, sc, k, tol, s, e_start, e_stop);
 }
 

@@ -37,6 +37,8 @@ void CGSolver::set_max_iter(int maxIter) { check(cgx_set_max_iter(m_ctx, maxIter
 
 void CGSolver::tolerance(double tolerance) { check(cgx_set_tolerance(m_ctx, tolerance), "tolerance"); }
 
+void CGSolver::set_preconditioner(int kind) { check(cgx_set_preconditioner(m_ctx, kind), "set_preconditioner"); }
+
 int CGSolver::m() const
 {
     int m = 0, n = 0;

@@ -45,6 +45,8 @@ public:
     void tolerance(double tolerance);
 
     // additions
+    /// CGX_PRECOND_NONE or CGX_PRECOND_JACOBI (include/cgx.h): takes effect at the next solve
+    void set_preconditioner(int kind);
     const cgx_result &last_result() const { return m_result; }
     int rank() const { return m_cfg.rank; }
     int psize() const { return m_cfg.nranks; }

@@ -11,6 +11,8 @@
 // `--loopback P` runs P logical row blocks on one GPU (CI stand-in for a multi-GPU node).
 // `--banded` (NOT a reference mode) holds the matrix as its non-zero diagonals: same recurrence and output, a
 // banded mat-vec instead of the dense GEMV; refused if the matrix has more than 64 diagonals.
+// `--jacobi` (NOT a reference mode) solves with the Jacobi preconditioner (include/cgx.h cgx_set_preconditioner): same stopping
+// test on sqrt(r.r) and the same output, usually fewer iterations on a matrix whose diagonal varies.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -131,6 +133,8 @@ int usage(const char *prog)
               << "                                  CG_WIREUP_TIMEOUT); a stage that does not come back ends the job with exit code 1\n"
               << "         --loopback P             P logical row blocks on one GPU\n"
               << "         --banded                 opt-in, not in the reference: store the non-zero diagonals only (<= 64)\n"
+              << "         --jacobi                 opt-in, not in the reference: Jacobi-preconditioned CG (z = D^-1 r; stops on\n"
+              << "                                  sqrt(r.r) < tol as without it; dense storage, per-launch loop)\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -146,7 +150,7 @@ int main(int argc, char **argv)
     // ---- split options from the reference's positional arguments -------------------------------------
     std::vector<std::string> pos;
     int ngpu = 1, loopback = 0;
-    bool stats = false, same_device = false, banded = false;
+    bool stats = false, same_device = false, banded = false, jacobi = false;
     std::string transport = "auto";
     std::string test_hang;   // --test-hang-stage
     double wireup_timeout = 120.0;
@@ -158,6 +162,7 @@ int main(int argc, char **argv)
         else if (a == "--loopback" && i + 1 < argc) loopback = atoi(argv[++i]);
         else if (a == "--stats") stats = true;
         else if (a == "--banded") banded = true;
+        else if (a == "--jacobi") jacobi = true;
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -381,6 +386,7 @@ int main(int argc, char **argv)
         }
         const int psize = cfg.nranks;
         CGSolver &solver = *holder;
+        if (jacobi) solver.set_preconditioner(CGX_PRECOND_JACOBI);   // every rank, before the first solve
 
         if (gen_form) solver.generate_lap2d_matrix(gen_n);   // cg_main.cc:31
         else solver.read_matrix(pos[0]);                     // code/CUDA/cg_main.cc:37
@@ -428,7 +434,9 @@ int main(int argc, char **argv)
                               << " gemv_GBps_per_gpu=" << (r.gemv_ms_avg > 0 ? r.gemv_bytes / (r.gemv_ms_avg * 1e-3) / 1e9 : 0.)
                               << " hbm_roofline_frac=" << (r.gemv_ms_avg > 0 ? r.gemv_bytes / (r.gemv_ms_avg * 1e-3) / 8.0e12 : 0.);
                 }
-                std::cerr << " persistent_launches_redone_per_launch=" << rec[8] << std::endl;
+                std::cerr << " persistent_launches_redone_per_launch=" << rec[8];
+                if (jacobi) std::cerr << " precond=jacobi";   // only when set: the plain line stays as it was
+                std::cerr << std::endl;
             }
         }
     } catch (const std::exception &e) {

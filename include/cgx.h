@@ -230,6 +230,18 @@ cgx_status  cgx_set_source_term(cgx_ctx *ctx, const double *b /* n doubles */);
 cgx_status  cgx_set_max_iter(cgx_ctx *ctx, int max_iter);
 cgx_status  cgx_set_tolerance(cgx_ctx *ctx, double tol);
 cgx_status  cgx_get_size(const cgx_ctx *ctx, int *m, int *n);   /* CGSolver::m(), n() */
+/* Preconditioner of the per-launch solver.  CGX_PRECOND_JACOBI: z = D^-1 r with D = diag(A), p0 = z0,
+ * alpha = r.z / p.Ap, beta = r.z(new) / r.z(old), p = z + beta p.  The stopping test and everything reported keep their meaning:
+ * sqrt(r.r) < tol, residual_prev / residual_last = sqrt(r.r).  The setting belongs to the context, survives new matrices and
+ * source terms, starts no GPU work, and takes effect at the next cgx_solve / cgx_solve_begin (between begin and end:
+ * CGX_ERR_BAD_ARG; every rank of a multi-rank run passes the same kind).  That begin extracts and gathers the diagonal once per
+ * matrix; an entry that is not finite and > 0 gives CGX_ERR_BAD_ARG on every rank (row and value in cgx_last_error).  While it
+ * is on, the loop runs on the per-launch path (also where the persistent kernels would take the problem); gemv_variant 40000 /
+ * 50000, CGX_MATRIX_BANDED and cgx_solve_multi give CGX_ERR_UNSUPPORTED.  Unknown kind: CGX_ERR_BAD_ARG. */
+#define CGX_PRECOND_NONE 0
+#define CGX_PRECOND_JACOBI 1
+cgx_status  cgx_set_preconditioner(cgx_ctx *ctx, int kind);
+cgx_status  cgx_get_preconditioner(const cgx_ctx *ctx, int *kind);
 /* Storage of local shard `local_shard`: *format = cgx_matrix_format; banded: *ndiag and offsets[0..*ndiag)
  * (column minus row, ascending; room for CGX_MAX_DIAGONALS ints or NULL); *matrix_bytes = device bytes of the block. */
 cgx_status  cgx_get_matrix_format(const cgx_ctx *ctx, int local_shard, int *format, int *ndiag, int *offsets,
