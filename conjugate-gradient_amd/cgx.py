@@ -18,6 +18,7 @@ UNIQUE_ID_BYTES = 128
 IPC_HANDLE_BYTES = 64
 COMM_SELF, COMM_LOOPBACK, COMM_RCCL, COMM_P2P = 0, 1, 2, 3
 MATRIX_DENSE, MATRIX_BANDED = 0, 1   # BANDED: opt-in fast path, not the reference's storage (include/cgx.h)
+MATRIX_CSR = 2                       # CSR: opt-in general sparse row block, not the reference's storage
 MAX_DIAGONALS = 64
 
 EXPORTS = [
@@ -34,6 +35,7 @@ EXPORTS = [
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
     "cgx_solve_multi", "cgx_probe_gemv_multi",
     "cgx_set_preconditioner", "cgx_get_preconditioner",
+    "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
@@ -125,6 +127,8 @@ def lib():
         L.cgx_set_tolerance.argtypes = [vp, C.c_double]
         L.cgx_get_size.argtypes = [vp, ip, ip]
         L.cgx_get_matrix_format.argtypes = [vp, C.c_int, ip, ip, ip, dp]
+        L.cgx_set_matrix_csr.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong), ip, dp]
+        L.cgx_get_matrix_nnz.argtypes = [vp, C.c_int, C.POINTER(C.c_longlong)]
         L.cgx_solve.argtypes = [vp, dp, C.POINTER(Result)]
         L.cgx_solve_begin.argtypes = [vp, dp]
         L.cgx_solve_steps.argtypes = [vp, C.c_int, ip]
@@ -307,6 +311,28 @@ class CGSolver:
         offs = (C.c_int * MAX_DIAGONALS)()
         self._check(lib().cgx_get_matrix_format(self._h, int(local_shard), C.byref(fmt), C.byref(nd), offs, C.byref(nbytes)))
         return fmt.value, list(offs[:nd.value]), nbytes.value
+
+    def matrix_nnz(self, local_shard=0):
+        """Entries stored for a local shard: rows*n (dense), ndiag*rows (banded), nnz (CSR)."""
+        nnz = C.c_longlong()
+        self._check(lib().cgx_get_matrix_nnz(self._h, int(local_shard), C.byref(nnz)))
+        return nnz.value
+
+    def set_matrix_csr(self, indptr, indices=None, data=None, n=None):
+        """The global n x n matrix as CSR (0-based; columns strictly ascending within a row).  indptr may also be any object
+        with .indptr / .indices / .data / .shape (a scipy.sparse CSR matrix, say); scipy itself is never imported."""
+        if hasattr(indptr, "indptr") and hasattr(indptr, "indices") and hasattr(indptr, "data"):
+            mat = indptr
+            if n is None:
+                n = int(mat.shape[0])
+            indptr, indices, data = mat.indptr, mat.indices, mat.data
+        indptr = np.ascontiguousarray(indptr, dtype=np.int64)
+        indices = np.ascontiguousarray(indices, dtype=np.int32)
+        data = np.ascontiguousarray(data, dtype=np.float64)
+        if n is None:
+            n = len(indptr) - 1
+        self._check(lib().cgx_set_matrix_csr(self._h, int(n), indptr.ctypes.data_as(C.POINTER(C.c_longlong)),
+                                             indices.ctypes.data_as(C.POINTER(C.c_int)), _dp(data)))
 
     # -- reference interface --------------------------------------------------------------------
     def generate_lap2d_matrix(self, size):

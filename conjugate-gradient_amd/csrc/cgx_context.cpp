@@ -80,6 +80,9 @@ void free_shard(Shard &s)
     }
     (void)hipFree(s.A);
     (void)hipFree(s.dia_vals);
+    (void)hipFree(s.csr_rp);
+    (void)hipFree(s.csr_col);
+    (void)hipFree(s.csr_vals);
     (void)hipFree(s.b_full);
     (void)hipFree(s.x);
     (void)hipFree(s.p[0]);
@@ -201,7 +204,7 @@ static cgx_status setup_resident(cgx_ctx *ctx, int variant)
     auto no = [&](const char *why) {
         return forced ? fail(ctx, CGX_ERR_UNSUPPORTED, std::string("gemv_variant 40000 / 50000 (persistent-kernel solver): ") + why) : CGX_OK;
     };
-    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->banded) return no("one GPU (CGX_COMM_SELF) and dense storage only");
+    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->sparse()) return no("one GPU (CGX_COMM_SELF) and dense storage only");
     if (!forced && ctx->n > 4096) {
         const char *smax = getenv("CGX_STREAM_MAX");
         if (ctx->n > (smax ? atoi(smax) : kStreamDefaultMax)) return CGX_OK;
@@ -245,11 +248,24 @@ static cgx_status setup_resident(cgx_ctx *ctx, int variant)
     return CGX_OK;
 }
 
+int configured_variant(const cgx_ctx *ctx)
+{
+    int variant = ctx->cfg.gemv_variant;
+    if (variant <= 0) {
+        const char *e = getenv("CGX_GEMV_VARIANT");
+        if (e) variant = atoi(e);
+    }
+    return variant;
+}
+
 // Allocate the shards for an n x n problem (matrix contents are filled by the caller).
 cgx_status setup_problem(cgx_ctx *ctx, int n)
 {
     if (n <= 0) return fail(ctx, CGX_ERR_BAD_ARG, "matrix size must be positive");
     if (n > (1 << 30)) return fail(ctx, CGX_ERR_UNSUPPORTED, "matrix size above 2^30 (indices are int, like the reference's)");
+    if (ctx->csr && !cgx::csr_variant_ok(configured_variant(ctx)))
+        return fail(ctx, CGX_ERR_UNSUPPORTED, "gemv_variant " + std::to_string(configured_variant(ctx)) +
+                                                  " on CSR storage: only 0 / -1 (the default) or 70000 + L (L = 1, 2, 4, ..., 64 lanes per row)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     if (!ctx->shards.empty() && ctx->n == n && ctx->lda == default_lda(ctx, n)) {
         // Same geometry as the current problem: keep every buffer.  (Freeing and re-allocating a multi-GiB matrix
@@ -297,11 +313,12 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
     // partial per chunk of the slice -- k_prefold_ap in front of the exchange, or the pushers of the fused P2P update.  That is
     // every multi-rank dense run and every fused P2P run; one GPU and banded storage keep K1's own partials in the tail.
     const bool fused_p2p = ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange;
-    ctx->chunked = (ctx->nranks > 1 && !ctx->banded) || fused_p2p;
-    const bool allow_split = ctx->chunked && !ctx->banded && ctx->nranks > 1;
+    ctx->chunked = (ctx->nranks > 1 && !ctx->sparse()) || fused_p2p;
+    const bool allow_split = ctx->chunked && !ctx->sparse() && ctx->nranks > 1;
     // (40000 = the LDS-resident solver, setup_resident below: set-up, verification and the probes still run the default K1)
     const int k1_variant = (variant == 40000 || variant == 50000) ? 0 : variant;
     auto plan_for = [&](int rows) {
+        if (ctx->csr) return cgx::plan_csr(rows, 0, k1_variant);   // grid by rows only; L follows the matrix (plan_csr_shards)
         return ctx->banded ? cgx::plan_dia(rows, k1_variant) : cgx::plan_gemv(k1_variant, rows, ctx->n, ctx->lda, allow_split);
     };
     int grid_max = 1;
@@ -374,12 +391,12 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
         s.plan = plan_for(s.rows);
         const size_t rows_alloc = (size_t)std::max(s.rows, 1);
         s.npartials = 3 * cgx::update_xr_grid(n) + 8;
-        if (!ctx->banded) HIP_TRY(ctx, hipMalloc(&s.A, rows_alloc * (size_t)ctx->lda * sizeof(double)));
+        if (!ctx->sparse()) HIP_TRY(ctx, hipMalloc(&s.A, rows_alloc * (size_t)ctx->lda * sizeof(double)));
         HIP_TRY(ctx, hipMalloc(&s.b_full, (size_t)n * sizeof(double)));
         const size_t apg_bytes = (size_t)ctx->nranks * ctx->seg_S * sizeof(double);
         const int rr_parts = cgx::update_xr_grid(n);   // one r.r partial per K3 workgroup
         const size_t rbuf_bytes = (size_t)(ctx->lda + rr_parts) * sizeof(double);
-        const bool blocks = ctx->cfg.comm_mode == CGX_COMM_SELF && !ctx->banded;   // where a persistent kernel may run the loop
+        const bool blocks = ctx->cfg.comm_mode == CGX_COMM_SELF && !ctx->sparse();   // where a persistent kernel may run the loop
         HIP_TRY(ctx, hipMalloc(&s.p[0], (size_t)ctx->lda * sizeof(double)));
         if (blocks) {
             static_assert(sizeof(Scalars) <= 16 * sizeof(double), "Scalars must fit the tail of a state block");
@@ -440,7 +457,7 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
 cgx_status plan_symmetric(cgx_ctx *ctx)
 {
     ctx->dinv_valid = false;   // behind every writer of A: the next preconditioned solve extracts the diagonal again
-    if (ctx->shards.size() != 1 || ctx->nranks != 1 || ctx->banded || ctx->chunked) return CGX_OK;
+    if (ctx->shards.size() != 1 || ctx->nranks != 1 || ctx->sparse() || ctx->chunked) return CGX_OK;
     Shard &s = ctx->shards[0];
     int variant = ctx->cfg.gemv_variant;
     if (variant <= 0) {
@@ -559,7 +576,7 @@ cgx_status cgx_create(cgx_ctx **out, const cgx_config *cfg_in)
         return fail(nullptr, CGX_ERR_BAD_ARG, "CGX_COMM_RCCL/P2P: rank out of range or nranks > 64");
     if (cfg.comm_mode < CGX_COMM_SELF || cfg.comm_mode > CGX_COMM_P2P)
         return fail(nullptr, CGX_ERR_BAD_ARG, "unknown comm_mode");
-    if (cfg.matrix_format != CGX_MATRIX_DENSE && cfg.matrix_format != CGX_MATRIX_BANDED)
+    if (cfg.matrix_format != CGX_MATRIX_DENSE && cfg.matrix_format != CGX_MATRIX_BANDED && cfg.matrix_format != CGX_MATRIX_CSR)
         return fail(nullptr, CGX_ERR_BAD_ARG, "unknown matrix_format");
 
     int ndev = 0;
@@ -575,6 +592,7 @@ cgx_status cgx_create(cgx_ctx **out, const cgx_config *cfg_in)
     ctx->device = cfg.device;
     ctx->nranks = cfg.nranks;
     ctx->banded = cfg.matrix_format == CGX_MATRIX_BANDED;
+    ctx->csr = cfg.matrix_format == CGX_MATRIX_CSR;
     if (ctx->cfg.check_every <= 0) ctx->cfg.check_every = 16;
     if (getenv("CGX_P2P_SEPARATE_EXCHANGE")) ctx->cfg.p2p_separate_exchange = 1;
 

@@ -122,6 +122,17 @@ __device__ __forceinline__ void tagged_store(unsigned long long *dst, double v, 
 }
 
 
+// One entry of generate_lap2d_matrix, cg.cc:178-185 (0 <= i, j < size).
+__device__ __forceinline__ double lap2d_entry(int size, int inc, long i, long j)
+{
+    if (j == i) return 4.0;                                      // cg.cc:183
+    if (i > 0 && j == i - 1) return -1.0;                        // cg.cc:182
+    if (i < size - 1 && j == i + 1) return -1.0;                 // cg.cc:184
+    if (i > inc && j == i - 1 - inc) return -1.0;                // cg.cc:181
+    if (i < size - 1 - inc && j == i + 1 + inc) return -1.0;     // cg.cc:185
+    return 0.0;                                                  // cg.cc:178-180
+}
+
 // ------------------------------------------------------------------------------------------------
 // shared by the per-launch GEMV kernels (cgx_kernels.hip: K1; cgx_symv.hip: the symmetric form)
 // ------------------------------------------------------------------------------------------------

@@ -23,6 +23,10 @@ struct Shard {
     double *A = nullptr;         // rows x lda, row-major, pad columns zero (CGX_MATRIX_DENSE)
     double *dia_vals = nullptr;  // CGX_MATRIX_BANDED: ndiag x dia.ld, the non-zero diagonals of the row block
     cgx::DiaView dia{};
+    long long *csr_rp = nullptr; // CGX_MATRIX_CSR: row pointers (rows + 1, local: csr_rp[0] = 0), global columns, values
+    int *csr_col = nullptr;
+    double *csr_vals = nullptr;
+    cgx::CsrView csr{};
     double *b_full = nullptr;    // n doubles: b is replicated like r (the reference builds the full b on every rank, cg.cc:218-234)
     // One GPU, dense storage (where the persistent kernels of cgx_resident.hip / cgx_stream.hip may run the loop): x, rbuf, p[1] and
     // sc are carved out of ONE block of solver state (cgx::state_off_*), and there are two such blocks -- a persistent launch
@@ -73,6 +77,8 @@ struct cgx_ctx {
     std::vector<double> b_host;
     bool have_matrix = false, have_b = false;
     bool banded = false;         // cfg.matrix_format == CGX_MATRIX_BANDED (opt-in, not the reference's storage)
+    bool csr = false;            // cfg.matrix_format == CGX_MATRIX_CSR (opt-in)
+    bool sparse() const { return banded || csr; }   // the storages whose K1 keeps its own partials (no dense-only paths)
     int precond = CGX_PRECOND_NONE;   // cgx_set_preconditioner: read by cgx_solve_begin, fixed until cgx_solve_end
     bool dinv_valid = false;     // every shard's dinv holds the diagonal of the current matrix (checked: finite and > 0)
     int *d_jbad = nullptr;       // device word: first row of a diagonal entry Jacobi cannot take (set-up only)
@@ -262,8 +268,13 @@ cgx_status setup_problem(cgx_ctx *ctx, int n);       // allocate the shards of a
 // exact symmetry on the device, and the plan becomes variant 6 or the general K1 accordingly (both ways).
 cgx_status plan_symmetric(cgx_ctx *ctx);
 
+int configured_variant(const cgx_ctx *ctx);   // cfg.gemv_variant, or CGX_GEMV_VARIANT where that is <= 0
+
 // cgx_matrix.cpp
 cgx_status alloc_dia(cgx_ctx *ctx, Shard &s, const std::vector<int> &offs);
+// CGX_MATRIX_CSR: (re)allocate shard s for nnz entries (row pointers zeroed), and the K1 plan once every shard is filled
+cgx_status alloc_csr(cgx_ctx *ctx, Shard &s, long long nnz);
+void plan_csr_shards(cgx_ctx *ctx);
 // A Matrix-Market coordinate file as MatrixCOO::read leaves it (matrix_coo.cc:7-60): sizes, symmetry, 0-based entries in
 // file order.  Host only; parsed on `nthreads` threads.
 struct MtxEntries {

@@ -47,7 +47,7 @@ void seg_finalize(SegView *sv);
 
 struct GemvPlan {
     int variant;     // 1 = column-split (p from L2 to registers), 2 = row-split (p tiles staged in LDS),
-                     // 3 = banded storage (DiaView), one thread per row
+                     // 3 = banded storage (DiaView), one thread per row; 7 = CSR storage (CsrView), R lanes per row
     int R;           // rows per wave (variant 2) or per workgroup (variant 1)
     int U;           // column-step unroll
     int waves;       // waves per workgroup
@@ -231,6 +231,33 @@ hipError_t launch_dia_mark(const double *A, long lda, int n, int row0, int rows,
 // dense row block -> banded storage for the offsets in dv
 hipError_t launch_dia_pack(const double *A, long lda, int n, int row0, int rows, double *vals, const DiaView &dv,
                            hipStream_t s);
+// ---- CSR storage (opt-in, cgx_csr.hip) -----------------------------------------------------
+// The row block as compressed sparse rows: row_ptr[0..rows] (local, row_ptr[0] = 0), col[] global column indices strictly
+// ascending within a row, vals[] the entries as given.
+struct CsrView {
+    const long long *row_ptr;
+    const int *col;
+    const double *vals;
+    long long nnz;
+};
+constexpr int kCsrVariantBase = 70000;   // cfg.gemv_variant 70000 + L forces L lanes per row (L = 1, 2, 4, ..., 64)
+// plan variant 7: R = L lanes per row, U = entries in flight per lane, waves = 4, grid = min(ceil(rows / 64), 2048) (a function
+// of rows only, so the exchange segment's geometry never depends on the matrix), rows_per_wg = 256 / L per pass.
+GemvPlan plan_csr(int rows, long long nnz, int variant);
+// variant <= 0 (the default) or 70000 + a power of two up to 64
+bool csr_variant_ok(int variant);
+// K1 on CSR storage: the contract of launch_spmv_dia_plain / launch_spmv_dia_fused, plus the Jacobi form (seg = z).
+hipError_t launch_spmv_csr_plain(const GemvPlan &plan, const CsrView &cv, int rows, int row0, long lda, const double *v_full,
+                                 double *Ap, double *partials, hipStream_t s);
+hipError_t launch_spmv_csr_fused(const GemvPlan &plan, const CsrView &cv, int rows, int row0, long lda, const double *p_old,
+                                 double *p_new, SegView seg, double *Ap, double *partials, Scalars *sc, int k, double tol,
+                                 hipStream_t s, hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr, bool jacobi = false);
+// generate_lap2d_matrix (cg.cc:159-188) straight into CSR: the non-zero entries of rows [row0, row0+rows), ascending columns.
+long long lap2d_csr_nnz(int size, int row0, int rows);
+hipError_t launch_csr_generate_lap2d(long long *row_ptr, int *col, double *vals, int size, int row0, int rows, hipStream_t s);
+// Jacobi set-up: dst[i] = the stored entry (row0 + i, row0 + i), or 0 where the row has none.
+hipError_t launch_csr_diag_slice(const CsrView &cv, int rows, int row0, double *dst, hipStream_t s);
+
 // ---- direct peer exchange (CGX_COMM_P2P): a lean all-gather over IPC-mapped mailboxes ---------------------
 // Every rank owns one fine-grained mailbox; all ranks map all mailboxes.  Layout (identical on every rank):
 //   flags : [kP2pChannels][kMaxRanks] words, one 128-B line each   (flag[c][q] = last epoch rank q delivered on channel c)

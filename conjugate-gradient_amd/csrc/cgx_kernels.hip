@@ -741,17 +741,7 @@ __global__ __launch_bounds__(256) void k_debug_norms(int count, const double *__
     }
 }
 
-// One entry of generate_lap2d_matrix, cg.cc:178-185 (0 <= i, j < size).
-__device__ __forceinline__ double lap2d_entry(int size, int inc, long i, long j)
-{
-    if (j == i) return 4.0;                                      // cg.cc:183
-    if (i > 0 && j == i - 1) return -1.0;                        // cg.cc:182
-    if (i < size - 1 && j == i + 1) return -1.0;                 // cg.cc:184
-    if (i > inc && j == i - 1 - inc) return -1.0;                // cg.cc:181
-    if (i < size - 1 - inc && j == i + 1 + inc) return -1.0;     // cg.cc:185
-    return 0.0;                                                  // cg.cc:178-180
-}
-
+// lap2d_entry (one entry of generate_lap2d_matrix) lives in cgx_device.h (shared with cgx_csr.hip).
 // generate_lap2d_matrix, cg.cc:159-188.  One thread writes 16 B; rows are 16-B aligned (lda even).
 __global__ __launch_bounds__(256) void k_generate_lap2d(double *__restrict__ A, long lda, int size, int row0, int rows,
                                                          int inc)

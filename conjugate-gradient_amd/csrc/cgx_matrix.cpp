@@ -1,6 +1,6 @@
 // cgx_matrix.cpp -- problem definition behind include/cgx.h: generate_lap2d_matrix (cg.cc:159-188), a caller's
 // dense matrix, the Matrix-Market reader (matrix_coo.cc:7-60 + matrix.cc:6-22), the source term (cg.cc:218-234),
-// for dense and for the opt-in banded storage.
+// for dense and for the opt-in banded and CSR storages.
 #include "cgx_internal.h"
 
 #include <sys/mman.h>
@@ -47,6 +47,54 @@ cgx_status alloc_dia(cgx_ctx *ctx, Shard &s, const std::vector<int> &offs)
     return CGX_OK;
 }
 
+cgx_status alloc_csr(cgx_ctx *ctx, Shard &s, long long nnz)
+{
+    (void)hipFree(s.csr_rp);
+    (void)hipFree(s.csr_col);
+    (void)hipFree(s.csr_vals);
+    s.csr_rp = nullptr;
+    s.csr_col = nullptr;
+    s.csr_vals = nullptr;
+    s.csr = cgx::CsrView{};
+    const size_t rp_bytes = ((size_t)std::max(s.rows, 0) + 1) * sizeof(long long), n1 = (size_t)std::max(nnz, 1LL);
+    HIP_TRY(ctx, hipMalloc(&s.csr_rp, rp_bytes));
+    HIP_TRY(ctx, hipMalloc(&s.csr_col, n1 * sizeof(int)));
+    HIP_TRY(ctx, hipMalloc(&s.csr_vals, n1 * sizeof(double)));
+    HIP_TRY(ctx, hipMemsetAsync(s.csr_rp, 0, rp_bytes, ctx->stream));
+    s.csr = cgx::CsrView{s.csr_rp, s.csr_col, s.csr_vals, nnz};
+    return CGX_OK;
+}
+
+// Behind every CSR writer: the lanes per row follow the shard's mean entries per row (the grid, and with it the segment
+// geometry, depends on the rows only).  A CSR problem never reaches the symmetric check or the persistent kernels.
+void plan_csr_shards(cgx_ctx *ctx)
+{
+    ctx->dinv_valid = false;
+    const int variant = configured_variant(ctx);
+    for (auto &s : ctx->shards) s.plan = cgx::plan_csr(s.rows, s.csr.nnz, variant);
+}
+
+namespace {
+
+// Upload shard s's rows of a CSR matrix held on the host: rp = the s.rows + 1 row pointers of the block (offsets into col and
+// vals, not necessarily starting at 0).
+cgx_status upload_csr_rows(cgx_ctx *ctx, Shard &s, const long long *rp, const int *col, const double *vals)
+{
+    const long long e0 = rp[0], nnz = rp[s.rows] - e0;
+    CGX_TRY(alloc_csr(ctx, s, nnz));
+    std::vector<long long> lrp((size_t)s.rows + 1);
+    for (int i = 0; i <= s.rows; ++i) lrp[(size_t)i] = rp[i] - e0;
+    HIP_TRY(ctx, hipMemcpyAsync(s.csr_rp, lrp.data(), lrp.size() * sizeof(long long), hipMemcpyHostToDevice, ctx->stream));
+    if (nnz > 0) {
+        HIP_TRY(ctx, hipMemcpyAsync(s.csr_col, col + e0, (size_t)nnz * sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(s.csr_vals, vals + e0, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // lrp is a local
+    return CGX_OK;
+}
+
+}  // namespace
+
 }  // namespace cgxi
 
 extern "C" {
@@ -56,12 +104,22 @@ cgx_status cgx_get_matrix_format(const cgx_ctx *ctx, int local_shard, int *forma
 {
     if (!ctx || local_shard < 0 || local_shard >= (int)ctx->shards.size() || !ctx->have_matrix) return CGX_ERR_BAD_ARG;
     const Shard &s = ctx->shards[local_shard];
-    if (format) *format = ctx->banded ? CGX_MATRIX_BANDED : CGX_MATRIX_DENSE;
+    if (format) *format = ctx->csr ? CGX_MATRIX_CSR : ctx->banded ? CGX_MATRIX_BANDED : CGX_MATRIX_DENSE;
     if (ndiag) *ndiag = ctx->banded ? s.dia.ndiag : 0;
     if (offsets && ctx->banded)
         for (int t = 0; t < s.dia.ndiag; ++t) offsets[t] = s.dia.off[t];
     if (matrix_bytes)
-        *matrix_bytes = ctx->banded ? 8.0 * (double)s.dia.ndiag * (double)s.dia.ld : 8.0 * (double)std::max(s.rows, 1) * (double)ctx->lda;
+        *matrix_bytes = ctx->csr      ? 12.0 * (double)s.csr.nnz + 8.0 * ((double)s.rows + 1.0)
+                        : ctx->banded ? 8.0 * (double)s.dia.ndiag * (double)s.dia.ld
+                                      : 8.0 * (double)std::max(s.rows, 1) * (double)ctx->lda;
+    return CGX_OK;
+}
+
+cgx_status cgx_get_matrix_nnz(const cgx_ctx *ctx, int local_shard, long long *nnz)
+{
+    if (!ctx || !nnz || local_shard < 0 || local_shard >= (int)ctx->shards.size() || !ctx->have_matrix) return CGX_ERR_BAD_ARG;
+    const Shard &s = ctx->shards[local_shard];
+    *nnz = ctx->csr ? s.csr.nnz : ctx->banded ? (long long)s.dia.ndiag * s.rows : (long long)s.rows * ctx->n;
     return CGX_OK;
 }
 
@@ -70,6 +128,17 @@ cgx_status cgx_generate_lap2d_matrix(cgx_ctx *ctx, int size)
 {
     if (!ctx) return CGX_ERR_BAD_ARG;
     CGX_TRY(setup_problem(ctx, size));
+    if (ctx->csr) {
+        // the non-zeros of cg.cc:181-185, written straight into CSR: no n x n block ever exists
+        for (auto &s : ctx->shards) {
+            CGX_TRY(alloc_csr(ctx, s, cgx::lap2d_csr_nnz(size, s.row0, s.rows)));
+            HIP_TRY(ctx, cgx::launch_csr_generate_lap2d(s.csr_rp, s.csr_col, s.csr_vals, size, s.row0, s.rows, ctx->stream));
+        }
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        plan_csr_shards(ctx);
+        ctx->have_matrix = true;
+        return CGX_OK;
+    }
     if (ctx->banded) {
         // the five diagonals of cg.cc:181-185, written straight into banded storage: no n x n block ever exists
         int off[5];
@@ -93,6 +162,27 @@ cgx_status cgx_set_matrix_dense(cgx_ctx *ctx, const double *A, long lda_host, in
 {
     if (!ctx || !A || lda_host < n) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_matrix_dense: bad argument");
     CGX_TRY(setup_problem(ctx, n));
+    if (ctx->csr) {
+        // packed on the host, row by row: the non-zero entries in ascending column order, then uploaded
+        for (auto &s : ctx->shards) {
+            std::vector<long long> rp((size_t)s.rows + 1, 0);
+            std::vector<int> col;
+            std::vector<double> vals;
+            for (int i = 0; i < s.rows; ++i) {
+                const double *row = A + (size_t)(s.row0 + i) * lda_host;
+                for (int j = 0; j < n; ++j)
+                    if (row[j] != 0.0) {
+                        col.push_back(j);
+                        vals.push_back(row[j]);
+                    }
+                rp[(size_t)i + 1] = (long long)col.size();
+            }
+            CGX_TRY(upload_csr_rows(ctx, s, rp.data(), col.data(), vals.data()));
+        }
+        plan_csr_shards(ctx);
+        ctx->have_matrix = true;
+        return CGX_OK;
+    }
     for (auto &s : ctx->shards) {
         if (s.rows <= 0) {
             if (ctx->banded) CGX_TRY(alloc_dia(ctx, s, {}));
@@ -388,6 +478,46 @@ cgx_status cgx_read_matrix(cgx_ctx *ctx, const char *path)
         return fail(ctx, CGX_ERR_UNSUPPORTED, "matrix has more than " + std::to_string(CGX_MAX_DIAGONALS) +
                                                   " non-zero diagonals: not a banded matrix (use CGX_MATRIX_DENSE)");
 
+    if (ctx->csr) {
+        // Matrix::read's sequential loop (matrix.cc:12-21) on the host: assignment (z, mirror) has sequence 2z + mirror; a
+        // stable sort by (row, column) keeps the sequence order within an element, and the last assignment wins.  Every
+        // assigned position is stored, an exact 0 included.
+        std::vector<long long> rp((size_t)n + 1, 0);
+        for (size_t z = 0; z < ha.size(); ++z)
+            for (int mir = 0; mir <= (is_sym ? 1 : 0); ++mir) {
+                const int i = mir ? hJ[z] : hI[z], j = mir ? hI[z] : hJ[z];
+                if (i >= 0 && i < n && j >= 0 && j < n) ++rp[(size_t)i + 1];
+            }
+        for (int i = 0; i < n; ++i) rp[(size_t)i + 1] += rp[(size_t)i];
+        std::vector<long long> fill(rp.begin(), rp.end() - 1);
+        std::vector<long long> seq((size_t)rp[(size_t)n]);   // by row, in sequence order (counting sort: stable)
+        for (size_t z = 0; z < ha.size(); ++z)
+            for (int mir = 0; mir <= (is_sym ? 1 : 0); ++mir) {
+                const int i = mir ? hJ[z] : hI[z], j = mir ? hI[z] : hJ[z];
+                if (i >= 0 && i < n && j >= 0 && j < n) seq[(size_t)fill[(size_t)i]++] = 2 * (long long)z + mir;
+            }
+        auto col_of = [&](long long q) { return (q & 1) ? hI[(size_t)(q >> 1)] : hJ[(size_t)(q >> 1)]; };
+        std::vector<long long> crp((size_t)n + 1, 0);
+        std::vector<int> col;
+        std::vector<double> vals;
+        col.reserve(seq.size());
+        vals.reserve(seq.size());
+        for (int i = 0; i < n; ++i) {
+            auto b = seq.begin() + rp[(size_t)i], e = seq.begin() + rp[(size_t)i + 1];
+            std::stable_sort(b, e, [&](long long x, long long y) { return col_of(x) < col_of(y); });
+            for (auto it = b; it != e; ++it) {
+                if (it + 1 != e && col_of(*(it + 1)) == col_of(*it)) continue;   // a later assignment to the same element
+                col.push_back(col_of(*it));
+                vals.push_back(ha[(size_t)(*it >> 1)]);
+            }
+            crp[(size_t)i + 1] = (long long)col.size();
+        }
+        for (auto &s : ctx->shards) CGX_TRY(upload_csr_rows(ctx, s, crp.data() + s.row0, col.data(), vals.data()));
+        plan_csr_shards(ctx);
+        ctx->have_matrix = true;
+        return CGX_OK;
+    }
+
     const size_t cnt = ha.size();
     struct DevBuf {
         void *p = nullptr;
@@ -416,6 +546,32 @@ cgx_status cgx_read_matrix(cgx_ctx *ctx, const char *path)
     }
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     CGX_TRY(plan_symmetric(ctx));
+    ctx->have_matrix = true;
+    return CGX_OK;
+}
+
+// ---- a caller's CSR matrix (CGX_MATRIX_CSR only) ---------------------------------------------------
+cgx_status cgx_set_matrix_csr(cgx_ctx *ctx, int n, const long long *row_ptr, const int *col_idx, const double *vals)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (!ctx->csr) return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_set_matrix_csr: the context's storage is not CGX_MATRIX_CSR");
+    if (n <= 0 || !row_ptr) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_matrix_csr: n must be positive and row_ptr non-null");
+    // everything is checked before anything is touched: a refused matrix leaves the context as it was
+    auto bad = [&](long long i, const std::string &why) {
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_matrix_csr: row " + std::to_string(i) + ": " + why);
+    };
+    if (row_ptr[0] != 0) return bad(0, "row_ptr[0] must be 0");
+    for (int i = 0; i < n; ++i)
+        if (row_ptr[i + 1] < row_ptr[i]) return bad(i, "row_ptr decreases");
+    if (row_ptr[n] > 0 && (!col_idx || !vals)) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_matrix_csr: col_idx and vals must be non-null");
+    for (int i = 0; i < n; ++i)
+        for (long long e = row_ptr[i]; e < row_ptr[i + 1]; ++e) {
+            if (col_idx[e] < 0 || col_idx[e] >= n) return bad(i, "column " + std::to_string(col_idx[e]) + " outside [0, n)");
+            if (e > row_ptr[i] && col_idx[e] <= col_idx[e - 1]) return bad(i, "columns not strictly ascending");
+        }
+    CGX_TRY(setup_problem(ctx, n));
+    for (auto &s : ctx->shards) CGX_TRY(upload_csr_rows(ctx, s, row_ptr + s.row0, col_idx, vals));
+    plan_csr_shards(ctx);
     ctx->have_matrix = true;
     return CGX_OK;
 }

@@ -61,7 +61,7 @@ cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in,
     if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": a cgx_solve_begin / cgx_solve_end pair is open");
     if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->nranks != 1 || ctx->shards.size() != 1)
         return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": one GPU only (CGX_COMM_SELF)");
-    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
     if (nrhs < 1 || nrhs > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nrhs must be 1 .. CGX_MAX_RHS");
     if (!in || !out) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
     if (ldin < ctx->n || ldout < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");

@@ -327,7 +327,7 @@ cgx_status cgx_probe_fill_matrix_hash(cgx_ctx *ctx, unsigned long long seed, int
     if (!ctx) return CGX_ERR_BAD_ARG;
     if (!ctx->have_matrix || ctx->shards.empty())
         return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_fill_matrix_hash: set a problem first (it defines n and the row blocks)");
-    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_probe_fill_matrix_hash: dense storage only");
+    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_probe_fill_matrix_hash: dense storage only");
     if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_fill_matrix_hash inside begin/end");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     for (auto &s : ctx->shards)
@@ -344,7 +344,19 @@ cgx_status cgx_probe_get_matrix_rows(cgx_ctx *ctx, int local_shard, double *A_ou
     Shard &s = ctx->shards[local_shard];
     if (row0) *row0 = s.row0;
     if (rows) *rows = s.rows;
-    if (A_out && s.rows > 0 && ctx->banded) {
+    if (A_out && s.rows > 0 && ctx->csr) {
+        // expand the rows on the host (a test probe, small sizes)
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        std::vector<long long> rp((size_t)s.rows + 1);
+        std::vector<int> col((size_t)std::max(s.csr.nnz, 1LL));
+        std::vector<double> vals(col.size());
+        HIP_TRY(ctx, hipMemcpy(rp.data(), s.csr_rp, rp.size() * sizeof(long long), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(col.data(), s.csr_col, col.size() * sizeof(int), hipMemcpyDeviceToHost));
+        HIP_TRY(ctx, hipMemcpy(vals.data(), s.csr_vals, vals.size() * sizeof(double), hipMemcpyDeviceToHost));
+        std::fill(A_out, A_out + (size_t)s.rows * ctx->n, 0.0);
+        for (int i = 0; i < s.rows; ++i)
+            for (long long e = rp[(size_t)i]; e < rp[(size_t)i + 1]; ++e) A_out[(size_t)i * ctx->n + (size_t)col[(size_t)e]] = vals[(size_t)e];
+    } else if (A_out && s.rows > 0 && ctx->banded) {
         // expand the diagonals on the host (a test probe, small sizes)
         HIP_TRY(ctx, hipSetDevice(ctx->device));
         std::vector<double> vals((size_t)std::max(s.dia.ndiag, 1) * (size_t)s.dia.ld);

@@ -129,7 +129,12 @@ cgx_status prepare_jacobi(cgx_ctx *ctx)
         s.zv.base = s.zbuf;
     }
     if (ctx->dinv_valid) return CGX_OK;
-    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_diag_slice(s.A, ctx->lda, s.rows, s.row0, s.Ap(), st));
+    for (auto &s : ctx->shards) {
+        if (ctx->csr)   // the entry with col == row, 0 where the row has none (then refused below like any entry <= 0)
+            HIP_TRY(ctx, cgx::launch_csr_diag_slice(s.csr, s.rows, s.row0, s.Ap(), st));
+        else
+            HIP_TRY(ctx, cgx::launch_diag_slice(s.A, ctx->lda, s.rows, s.row0, s.Ap(), st));
+    }
     CGX_TRY(gather_segments(ctx, false));
     if (!ctx->d_jbad) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_jbad), sizeof(int)));
     HIP_TRY(ctx, hipMemsetAsync(ctx->d_jbad, 0x7f, sizeof(int), st));   // 0x7f7f7f7f: above every row index
@@ -190,7 +195,9 @@ namespace cgxi {
 // K1, plain form (vector given): initial residual, DEBUG verification, probes.
 cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full)
 {
-    if (ctx->banded)
+    if (ctx->csr)
+        HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, ctx->lda, v_full, s.Ap(), s.k1_part(), ctx->stream));
+    else if (ctx->banded)
         HIP_TRY(ctx, cgx::launch_spmv_dia_plain(s.plan, s.dia, s.rows, s.row0, ctx->n, ctx->lda, v_full, s.Ap(), s.k1_part(), s.sc,
                                                 ctx->stream));
     else if (s.plan.variant == 6)   // exactly symmetric A, one shard (cgx_symv.hip)
@@ -232,7 +239,10 @@ cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
     }
     hipEvent_t m1 = (timed && ctx->cfg.profile_markers) ? ctx->ev_pool[ctx->ev_used - 1] : nullptr;
     const bool pc = ctx->precond == CGX_PRECOND_JACOBI;   // p = z + beta p_old: K1 reads z where it reads r otherwise
-    if (ctx->banded)
+    if (ctx->csr)
+        HIP_TRY(ctx, cgx::launch_spmv_csr_fused(s.plan, s.csr, s.rows, s.row0, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1], pc ? s.zv : s.rv,
+                                                s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1, pc));
+    else if (ctx->banded)
         HIP_TRY(ctx, cgx::launch_spmv_dia_fused(s.plan, s.dia, s.rows, s.row0, ctx->n, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1],
                                                 s.rv, s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1));
     else if (s.plan.variant == 6)   // the event pair spans the tile kernel and the fold: all the work that produces Ap
@@ -781,8 +791,10 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
             if (v.size() % 2 == 0) med = 0.5 * (med + *std::max_element(v.begin(), v.begin() + mid));
             res->gemv_ms_median = med;
         }
-        res->gemv_bytes = ctx->banded ? 8.0 * ((double)s0.rows * s0.dia.ndiag + 2.0 * s0.rows)
-                                      : 8.0 * ((double)s0.rows * ctx->n + ctx->n + s0.rows);
+        // CSR: values, columns, row pointers, Ap written and p read once (the dense definition's counterpart)
+        res->gemv_bytes = ctx->csr      ? 12.0 * (double)s0.csr.nnz + 8.0 * ((double)s0.rows + 1) + 8.0 * s0.rows + 8.0 * ctx->n
+                          : ctx->banded ? 8.0 * ((double)s0.rows * s0.dia.ndiag + 2.0 * s0.rows)
+                                        : 8.0 * ((double)s0.rows * ctx->n + ctx->n + s0.rows);
     }
     return CGX_OK;
 }

@@ -11,6 +11,8 @@
 // `--loopback P` runs P logical row blocks on one GPU (CI stand-in for a multi-GPU node).
 // `--banded` (NOT a reference mode) holds the matrix as its non-zero diagonals: same recurrence and output, a
 // banded mat-vec instead of the dense GEMV; refused if the matrix has more than 64 diagonals.
+// `--csr` (NOT a reference mode) holds the matrix as compressed sparse rows (any sparsity pattern): same recurrence and
+// output, a CSR mat-vec instead of the dense GEMV.  Not together with --banded.
 // `--jacobi` (NOT a reference mode) solves with the Jacobi preconditioner (include/cgx.h cgx_set_preconditioner): same stopping
 // test on sqrt(r.r) and the same output, usually fewer iterations on a matrix whose diagonal varies.
 #include <signal.h>
@@ -133,8 +135,10 @@ int usage(const char *prog)
               << "                                  CG_WIREUP_TIMEOUT); a stage that does not come back ends the job with exit code 1\n"
               << "         --loopback P             P logical row blocks on one GPU\n"
               << "         --banded                 opt-in, not in the reference: store the non-zero diagonals only (<= 64)\n"
+              << "         --csr                    opt-in, not in the reference: store compressed sparse rows (any pattern;\n"
+              << "                                  not together with --banded)\n"
               << "         --jacobi                 opt-in, not in the reference: Jacobi-preconditioned CG (z = D^-1 r; stops on\n"
-              << "                                  sqrt(r.r) < tol as without it; dense storage, per-launch loop)\n"
+              << "                                  sqrt(r.r) < tol as without it; dense or CSR storage, per-launch loop)\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -150,7 +154,7 @@ int main(int argc, char **argv)
     // ---- split options from the reference's positional arguments -------------------------------------
     std::vector<std::string> pos;
     int ngpu = 1, loopback = 0;
-    bool stats = false, same_device = false, banded = false, jacobi = false;
+    bool stats = false, same_device = false, banded = false, csr = false, jacobi = false;
     std::string transport = "auto";
     std::string test_hang;   // --test-hang-stage
     double wireup_timeout = 120.0;
@@ -162,6 +166,7 @@ int main(int argc, char **argv)
         else if (a == "--loopback" && i + 1 < argc) loopback = atoi(argv[++i]);
         else if (a == "--stats") stats = true;
         else if (a == "--banded") banded = true;
+        else if (a == "--csr") csr = true;
         else if (a == "--jacobi") jacobi = true;
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
@@ -177,6 +182,10 @@ int main(int argc, char **argv)
         else pos.push_back(a);
     }
     if (pos.empty()) return usage(argv[0]);   // cg_main.cc:22-26 (returns 1)
+    if (csr && banded) {
+        std::cerr << argv[0] << ": --csr and --banded are two storages: give one of them\n";
+        return usage(argv[0]);
+    }
     if (ngpu < 1) ngpu = 1;
 
     int gen_n = 0;
@@ -287,7 +296,7 @@ int main(int argc, char **argv)
         cgx_config cfg;
         cgx_config_init(&cfg);
         cfg.profile_gemv = stats ? 1 : 0;
-        cfg.matrix_format = banded ? CGX_MATRIX_BANDED : CGX_MATRIX_DENSE;
+        cfg.matrix_format = csr ? CGX_MATRIX_CSR : banded ? CGX_MATRIX_BANDED : CGX_MATRIX_DENSE;
         std::unique_ptr<CGSolver> holder;
         if (ngpu > 1) {
             cfg.nranks = ngpu;
@@ -419,7 +428,13 @@ int main(int argc, char **argv)
                 const bool persistent = plan[0] == 4 || plan[0] == 5;
                 std::cerr << "cgsolver stats: n=" << n << " gpus=" << psize << " loop_bodies=" << it
                           << " loop_s=" << r.seconds_loop << " iterations_per_s=" << (r.seconds_loop > 0 ? it / r.seconds_loop : 0.)
-                          << " format=" << (banded ? "banded" : "dense")
+                          << " format=" << (csr ? "csr" : banded ? "banded" : "dense");
+                if (csr) {
+                    long long nnz = 0;
+                    (void)cgx_get_matrix_nnz(solver.context(), 0, &nnz);
+                    std::cerr << " nnz=" << nnz;
+                }
+                std::cerr
                           << " loop=" << (plan[0] == 4 ? "resident-kernel" : plan[0] == 5 ? "streaming-persistent-kernel" : "per-launch");
                 if (persistent) {
                     // no K1 launches to time: the whole loop against the algorithmic bytes of its GEMVs, and what its waits cost

@@ -60,10 +60,16 @@ typedef enum cgx_comm_mode {
  * most CGX_MAX_DIAGONALS of them) and K1 becomes a banded mat-vec -- same CG recurrence, same results to rounding,
  * n/ndiag times less matrix traffic (the reference's unused MatrixCOO::mat_vec,
  * code/MPI/matrix_coo.hh:22-34, is the hint).  A matrix with more diagonals is refused with
- * CGX_ERR_UNSUPPORTED, never silently densified. */
+ * CGX_ERR_UNSUPPORTED, never silently densified.
+ * CSR is a second OPT-IN storage, also NOT in the reference and never used by bench.py: a general sparse row block
+ * (compressed sparse rows, global column indices) for matrices that are neither small enough to be
+ * dense nor banded.  K1 becomes a CSR mat-vec (plan variant 7); K3, every transport and the Jacobi preconditioner are shared.
+ * No n x n or rows x n buffer exists at any point of a CSR ingest.  cgx_read_matrix on CSR keeps every position the file
+ * assigns, also where the resolved value is exactly 0 (stored as an explicit zero). */
 typedef enum cgx_matrix_format {
     CGX_MATRIX_DENSE = 0,
-    CGX_MATRIX_BANDED = 1
+    CGX_MATRIX_BANDED = 1,
+    CGX_MATRIX_CSR = 2
 } cgx_matrix_format;
 #define CGX_MAX_DIAGONALS 64
 
@@ -141,7 +147,8 @@ typedef struct cgx_result {
     double gemv_ms_avg;       /* mean K1 launch duration (HIP events) over the most recent cgx_solve_steps call, 0 if not profiled */
     double gemv_ms_min;
     long long gemv_launches;  /* K1 launches that were event-timed (= samples behind avg / min / median / max) */
-    double gemv_bytes;        /* algorithmic bytes of ONE K1 launch on this shard: 8*(rows*n + n + rows); banded: 8*(rows*ndiag + 2*rows) */
+    double gemv_bytes;        /* algorithmic bytes of ONE K1 launch on this shard: 8*(rows*n + n + rows); banded: 8*(rows*ndiag + 2*rows);
+                                 CSR: 8*nnz + 4*nnz + 8*(rows+1) + 8*rows + 8*n */
     double gemv_ms_median;    /* median of the samples (SURVEY.md section 8d asks for the median) */
     double gemv_ms_max;
     long long gemv_discarded; /* launches deliberately not sampled although profiling was on: the first one after a drained stream */
@@ -179,7 +186,10 @@ cgx_status  cgx_get_comm_info(cgx_ctx *ctx, int *comm_mode, int *ranks_wired, in
  * Variant 6 = one GPU, dense, n > 16384, the default plan and an A that equals its transpose bit for bit (checked on the device
  * behind every writer of A): A p from the upper triangle's B x B tiles (csrc/cgx_symv.hip); then R = B, U = tiles of the longest
  * workgroup run, waves = 4, light = workgroups of the fold kernel (= p.Ap partials), split = nb = ceil(n / B) (slots per row of
- * the partial buffer), grid = workgroups of the tile kernel, ncols as for variant 1.  After a persistent launch has been redone on the per-launch path (gemv_variant
+ * the partial buffer), grid = workgroups of the tile kernel, ncols as for variant 1.
+ * Variant 7 = CSR storage (csrc/cgx_csr.hip): R = L, lanes of a wave64 per row (1 ... 64; default from the mean entries per
+ * row, gemv_variant 70000 + L forces it), U = entries in flight per lane, waves = waves per workgroup (4), light = 0, split = 1,
+ * grid = workgroups (min(ceil(rows / 64), 2048), striding above that), ncols as for variant 1.  After a persistent launch has been redone on the per-launch path (gemv_variant
  * above) this reports the per-launch shape. */
 #define CGX_GEMV_PLAN_INTS 8
 cgx_status  cgx_get_gemv_plan(const cgx_ctx *ctx, int local_shard, int out[CGX_GEMV_PLAN_INTS]);
@@ -222,6 +232,12 @@ cgx_status  cgx_set_matrix_dense(cgx_ctx *ctx, const double *A, long lda, int n)
  * without a dense n*n host staging copy.  Entries are assigned on the device in the file's order (a later
  * entry for the same element wins, a symmetric entry's mirror follows it), exactly as the sequential loop. */
 cgx_status  cgx_read_matrix(cgx_ctx *ctx, const char *mtx_path);
+/* CGX_MATRIX_CSR only (any other storage: CGX_ERR_UNSUPPORTED): the global n x n matrix as compressed sparse rows in host
+ * arrays, 0-based: row_ptr[0] == 0, row_ptr non-decreasing, row_ptr[n] = nnz; the columns of a row strictly ascending and in
+ * [0, n).  Each shard copies its own rows; values are stored as given, explicit zeros included.  A null pointer, n <= 0 or a
+ * broken rule gives CGX_ERR_BAD_ARG (cgx_last_error names the first bad row) and leaves the context as it was.  Sets m = n,
+ * max_iter = n. */
+cgx_status  cgx_set_matrix_csr(cgx_ctx *ctx, int n, const long long *row_ptr, const int *col_idx, const double *vals);
 /* CGSolver::init_source_term(h), cg.cc:218-234: b evaluated on the HOST with libm sin so it is
  * bit-identical to the reference's, then this shard's slice is uploaded. */
 cgx_status  cgx_init_source_term(cgx_ctx *ctx, double h);
@@ -246,6 +262,9 @@ cgx_status  cgx_get_preconditioner(const cgx_ctx *ctx, int *kind);
  * (column minus row, ascending; room for CGX_MAX_DIAGONALS ints or NULL); *matrix_bytes = device bytes of the block. */
 cgx_status  cgx_get_matrix_format(const cgx_ctx *ctx, int local_shard, int *format, int *ndiag, int *offsets,
                                   double *matrix_bytes);
+/* Entries stored for local shard `local_shard`: rows * n (dense), ndiag * rows (banded), the shard's nnz (CSR).  CSR's
+ * cgx_get_matrix_format gives ndiag = 0 and matrix_bytes = 12 * nnz + 8 * (rows + 1) (values, columns, row pointers). */
+cgx_status  cgx_get_matrix_nnz(const cgx_ctx *ctx, int local_shard, long long *nnz);
 
 /* ---- CGSolver::solve, cg.cc:38-156 ------------------------------------------------------- */
 /* x: n doubles, in = initial guess (cg_main.cc:49-50 passes zeros), out = solution (every rank

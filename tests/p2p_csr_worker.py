@@ -1,0 +1,58 @@
+"""Worker for tests/test_gpu_csr.py: one OS process per rank, all on ONE GPU, over the CGX_COMM_P2P mailboxes, CSR storage.  Every
+rank solves the generated matrix (diagonal 4) plainly and with Jacobi on the same context; rank 0 writes "same bits" if x and the
+reported numbers agree bit for bit on every rank.  argv: n max_iter out tagged(0|1)"""
+import os
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import __graft_entry__ as g  # noqa: E402
+
+
+def main():
+    n, iters, out, tagged = int(sys.argv[1]), int(sys.argv[2]), sys.argv[3], sys.argv[4] == "1"
+    dist.init_process_group(backend="gloo")
+    rank, world = dist.get_rank(), dist.get_world_size()
+    assert torch.cuda.is_available()
+    pkg = g.load_package()
+    s = pkg.CGSolver(comm_mode=pkg.COMM_P2P, nranks=world, rank=rank, device=0, p2p_timeout_ms=20000, p2p_tagged=tagged,
+                     matrix_format=pkg.MATRIX_CSR)
+    mine = torch.tensor(list(s.p2p_export()), dtype=torch.uint8)
+    allh = [torch.zeros_like(mine) for _ in range(world)]
+    dist.all_gather(allh, mine)
+    s.p2p_import(b"".join(bytes(t.tolist()) for t in allh))
+    dist.barrier()
+    assert s.p2p_selftest(16)
+    dist.barrier()
+    s.generate_lap2d_matrix(n)
+    assert s.gemv_plan()["variant"] == 7
+    keys = ("iterations", "converged", "residual_prev", "residual_last", "rel_residual", "x_norm")
+    runs = []
+    for kind, tol in ((None, 0.0), ("jacobi", 0.0), (None, 1e-3), ("jacobi", 1e-3)):
+        s.set_preconditioner(kind)   # every rank, the same value
+        s.set_max_iter(iters if tol == 0.0 else 4 * n)
+        s.tolerance(tol)
+        s.init_source_term(1.0 / n)
+        x = np.zeros(n)
+        dist.barrier()
+        res = s.solve(x)
+        runs.append((x, [float(res[k]) for k in keys]))
+    ok = all(np.array_equal(runs[i][0].view(np.uint64), runs[i + 1][0].view(np.uint64)) and runs[i][1] == runs[i + 1][1]
+             for i in (0, 2))
+    ok = ok and runs[3][1][1] == 1.0   # the tolerance run converged
+    flags = [torch.zeros(1) for _ in range(world)]
+    dist.all_gather(flags, torch.tensor([1.0 if ok else 0.0]))
+    s.close()
+    dist.barrier()
+    dist.destroy_process_group()
+    if rank == 0:
+        with open(out, "w") as f:
+            f.write("same bits" if all(float(t) == 1.0 for t in flags) else "differ: %r" % ([r[1] for r in runs],))
+
+
+if __name__ == "__main__":
+    main()
