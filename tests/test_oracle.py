@@ -467,3 +467,50 @@ def test_oracle_agrees_with_the_recurrence_through_a_real_openblas(oracle, refer
             assert kb == rows[0]["k"] and abs(resb - rows[0]["residual"]) <= 1e-6 * rows[0]["residual"]
         else:
             assert abs(kb - rows[0]["k"]) <= 0.15 * rows[0]["k"]
+
+
+# ---- the exact oracle of tests/test_gpu_jacobi_scaled.py: scaling by powers of two commutes with the recurrence -------------
+def _cg_numpy(A, b, iters, dinv=None):
+    """Plain CG (dinv None) or Jacobi PCG from x0 = 0 in numpy float64, tol = 0: the library's recurrence
+    without the alpha safeguard, which the well-conditioned problems here never reach."""
+    x = np.zeros_like(b)
+    r = b.copy()
+    z = r if dinv is None else dinv * r
+    p = z.copy()
+    rho = r @ z
+    for _ in range(iters):
+        Ap = A @ p
+        alpha = rho / (p @ Ap)
+        x = x + alpha * p
+        r = r - alpha * Ap
+        z = r if dinv is None else dinv * r
+        rn = r @ z
+        p = z + (rn / rho) * p
+        rho = rn
+    return x
+
+
+@pytest.mark.parametrize("matrix,n,iters", [("lap2d", 1024, 80), ("lap2d", 3001, 80), ("hash", 1500, 40)])
+def test_power_of_two_scaling_commutes_with_jacobi_pcg(oracle, matrix, n, iters):
+    """L with one power of two c on its diagonal, s_i = 2**e_i with e_i in [-8, 8] differing from row to row, A = S L S,
+    b = S b~: Jacobi PCG on (A, b) gives x with s * x equal to plain CG's x~ on (L, b~) BIT FOR BIT, because every quantity of
+    the one recurrence is the other's times a power of two (r = S r~, z = r~ / (c s), p = S^-1 p~ / c, alpha_J = c alpha), and
+    such a factor commutes with every rounding.  A dinv that belongs to the neighbouring row -- what a uniform diagonal cannot
+    show -- moves x by far more than 1e-3."""
+    L = oracle.generate_lap2d(n) if matrix == "lap2d" else oracle.hash_rows(n, 0, n, 0x7AC0B1, True, 2048.0)
+    c = L[0, 0]
+    assert np.all(np.diag(L) == c) and np.log2(c) == int(np.log2(c)) and np.array_equal(L, L.T)
+    e = np.random.default_rng(n).integers(-8, 9, n)
+    assert e.min() == -8 and e.max() == 8
+    s = np.ldexp(1.0, e)
+    A = (s[:, None] * L) * s[None, :]
+    assert np.array_equal(A, A.T) and np.array_equal(np.diag(A), c * s * s)
+    bt = oracle.init_source_term(n)
+    xt = _cg_numpy(L, bt, iters)
+    assert np.all(np.isfinite(xt)) and np.linalg.norm(xt) > 0
+    dinv = 1.0 / np.diag(A)
+    xj = _cg_numpy(A, s * bt, iters, dinv)
+    assert np.array_equal((s * xj).view(np.uint64), xt.view(np.uint64))
+    xbad = _cg_numpy(A, s * bt, iters, np.roll(dinv, 1))
+    assert np.all(np.isfinite(xbad))
+    assert np.linalg.norm(s * xbad - xt) > 1e-3 * np.linalg.norm(xt)
