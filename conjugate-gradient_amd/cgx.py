@@ -35,11 +35,13 @@ EXPORTS = [
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
     "cgx_solve_multi", "cgx_probe_gemv_multi",
     "cgx_set_preconditioner", "cgx_get_preconditioner",
+    "cgx_set_preconditioner_block", "cgx_get_preconditioner_block", "cgx_probe_get_precond_blocks",
     "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 _PRECOND_NAMES = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI}
+PRECOND_BLOCKS = (1, 2, 4, 8, 16, 32, 64, 128, 256)   # cgx_set_preconditioner_block
 
 
 class Config(C.Structure):
@@ -152,6 +154,9 @@ def lib():
         L.cgx_solve_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
+        L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
+        L.cgx_get_preconditioner_block.argtypes = [vp, ip]
+        L.cgx_probe_get_precond_blocks.argtypes = [vp, C.c_int, dp]
         L.cgx_probe_gemv_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, dp]
         L.cgx_probe_parse_matrix_market.argtypes = [C.c_char_p, C.c_int, ip, ip, ip, ip, ip, ip, dp, C.c_long, C.c_char_p, C.c_int]
         for name in EXPORTS:
@@ -359,11 +364,26 @@ class CGSolver:
     def tolerance(self, tol):
         self._check(lib().cgx_set_tolerance(self._h, float(tol)))
 
-    def set_preconditioner(self, kind):
-        """None (plain CG) or "jacobi": takes effect at the next solve (include/cgx.h cgx_set_preconditioner)."""
+    def set_preconditioner(self, kind, block=1):
+        """None (plain CG) or "jacobi": takes effect at the next solve (include/cgx.h cgx_set_preconditioner).  block > 1 makes
+        "jacobi" block Jacobi with the block x block diagonal blocks (cgx_set_preconditioner_block; 1 = point Jacobi)."""
         if kind not in _PRECOND_NAMES:
             raise ValueError("preconditioner must be None or 'jacobi', not %r" % (kind,))
+        if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in PRECOND_BLOCKS:
+            raise ValueError("block must be one of %r, not %r" % (PRECOND_BLOCKS, block))
         self._check(lib().cgx_set_preconditioner(self._h, _PRECOND_NAMES[kind]))
+        self._check(lib().cgx_set_preconditioner_block(self._h, int(block)))
+
+    def preconditioner_block(self):
+        b = C.c_int()
+        self._check(lib().cgx_get_preconditioner_block(self._h, C.byref(b)))
+        return b.value
+
+    def _probe_precond_blocks(self, local_shard=0):
+        """Test hook: the block inverses of a local shard as an (n, block) array, row i = (D_b^-1)(i, s(i) : s(i) + block)."""
+        W = np.zeros((self.n(), self.preconditioner_block()), dtype=np.float64)
+        self._check(lib().cgx_probe_get_precond_blocks(self._h, int(local_shard), _dp(W)))
+        return W
 
     @property
     def preconditioner(self):

@@ -94,6 +94,7 @@ void free_shard(Shard &s)
     (void)hipFree(s.k1_scratch);
     (void)hipFree(s.sym_parts);
     (void)hipFree(s.dinv);
+    (void)hipFree(s.W);
     (void)hipFree(s.zbuf);
     (void)hipFree(s.sc);
     (void)hipFree(s.gathered);
@@ -955,6 +956,26 @@ cgx_status cgx_get_preconditioner(const cgx_ctx *ctx, int *kind)
 {
     if (!ctx || !kind) return CGX_ERR_BAD_ARG;
     *kind = ctx->precond;
+    return CGX_OK;
+}
+
+cgx_status cgx_set_preconditioner_block(cgx_ctx *ctx, int block)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (!cgx::bj_block_ok(block))
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_block: block must be 1, 2, 4, ..., 256, not " + std::to_string(block));
+    if (ctx->in_solve)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_block: called between cgx_solve_begin and cgx_solve_end");
+    // host bookkeeping only: the blocks are extracted and inverted (collectively) by the next preconditioned cgx_solve_begin
+    if (block != ctx->precond_block) ctx->dinv_valid = false;
+    ctx->precond_block = block;
+    return CGX_OK;
+}
+
+cgx_status cgx_get_preconditioner_block(const cgx_ctx *ctx, int *block)
+{
+    if (!ctx || !block) return CGX_ERR_BAD_ARG;
+    *block = ctx->precond_block;
     return CGX_OK;
 }
 

@@ -152,6 +152,26 @@ __global__ __launch_bounds__(256) void k_csr_diag_slice(CsrView cv, int rows, in
     }
 }
 
+// Block-Jacobi set-up: k_bj_col_slice on CSR storage -- the entry (row0 + i, s(row0 + i) + t) found as
+// k_csr_diag_slice finds the diagonal, 0 where the row stores none or the column lies past n.
+__global__ __launch_bounds__(256) void k_csr_bj_col_slice(CsrView cv, int n, int rows, int row0, int block, int t0,
+                                                           double *__restrict__ dst, long dst_stride)
+{
+    const int t = t0 + (int)blockIdx.y;
+    double *d = dst + (long)blockIdx.y * dst_stride;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long)gridDim.x * 256) {
+        const long g = row0 + i;
+        const long c = g - g % block + t;
+        long long lo = cv.row_ptr[i], hi = cv.row_ptr[i + 1];
+        while (lo < hi) {
+            const long long mid = lo + (hi - lo) / 2;
+            if (cv.col[mid] < c) lo = mid + 1;
+            else hi = mid;
+        }
+        d[i] = (c < n && lo < cv.row_ptr[i + 1] && cv.col[lo] == c) ? cv.vals[lo] : 0.0;
+    }
+}
+
 struct CsrArgs {
     CsrView cv;
     int rows, row0;
@@ -266,6 +286,15 @@ hipError_t launch_csr_diag_slice(const CsrView &cv, int rows, int row0, double *
 {
     if (rows <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_csr_diag_slice, dim3(capped_grid(rows, 1024)), dim3(256), 0, s, cv, rows, row0, dst);
+    return hipGetLastError();
+}
+
+hipError_t launch_csr_bj_col_slice(const CsrView &cv, int n, int rows, int row0, int block, int t0, int nt, double *dst,
+                                   long dst_stride, hipStream_t s)
+{
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_csr_bj_col_slice, dim3(capped_grid(rows, 1024), nt), dim3(256), 0, s, cv, n, rows, row0, block, t0, dst,
+                       dst_stride);
     return hipGetLastError();
 }
 

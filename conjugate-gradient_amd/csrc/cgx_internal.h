@@ -53,6 +53,10 @@ struct Shard {
     // ([z | r.z partials | r.r partials], cgx::SegView zv: rv's geometry)
     double *dinv = nullptr;
     double *zbuf = nullptr;
+    // block Jacobi: the replicated block inverses, W[t * lda + i] = (D_b^-1)(i, s(i) + t); w_block x lda
+    // doubles, made at the first solve with cgx_set_preconditioner_block > 1, remade when the block size changes
+    double *W = nullptr;
+    int w_block = 0;
     cgx::SegView zv{};
     int npartials = 0;
     double *Ap() const { return apg + (size_t)rank * apv.S; }          // this shard's Ap slice (K1 output)
@@ -80,7 +84,9 @@ struct cgx_ctx {
     bool csr = false;            // cfg.matrix_format == CGX_MATRIX_CSR (opt-in)
     bool sparse() const { return banded || csr; }   // the storages whose K1 keeps its own partials (no dense-only paths)
     int precond = CGX_PRECOND_NONE;   // cgx_set_preconditioner: read by cgx_solve_begin, fixed until cgx_solve_end
-    bool dinv_valid = false;     // every shard's dinv holds the diagonal of the current matrix (checked: finite and > 0)
+    int precond_block = 1;       // cgx_set_preconditioner_block: 1 = point Jacobi (dinv), > 1 = block Jacobi (W); read at begin
+    bool dinv_valid = false;     // every shard's dinv (block 1) / W (block > 1) holds the checked inverse of the current matrix's
+                                 // diagonal (blocks) for precond_block: lowered behind every writer of A and by a new block size
     int *d_jbad = nullptr;       // device word: first row of a diagonal entry Jacobi cannot take (set-up only)
     bool res_parked = false;     // the persistent kernel would take this problem, but the preconditioner keeps it on the per-launch path
 

@@ -126,7 +126,8 @@ hipError_t launch_prefold_ap(const double *parts, int split, long stride, int ro
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s,
                             hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr,   // optional: bound to the dispatch
-                            const double *dinv = nullptr, SegView zv = SegView{});
+                            const double *dinv = nullptr, SegView zv = SegView{},
+                            const double *W = nullptr, int block = 1, long lda = 0);   // W != nullptr: block Jacobi, see below
 int update_xr_grid(int count);   // ceil(count/256), at most kMaxVectorGrid (above that the kernels stride over the rows)
 constexpr int kMaxVectorGrid = 1024;
 
@@ -141,7 +142,8 @@ hipError_t launch_reduce_partials3(const double *partials, int n, double *out3, 
 // Initial residual (cg.cc:79-85): r = b - Ap for all n rows (Ap from the gathered segments); rv tail[wg] = sum r_i^2.
 // dinv != nullptr (Jacobi): also z0 = dinv * r0 into zv, the r.z partials in zv's tail and the r.r partials behind them.
 hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
-                                const double *dinv = nullptr, SegView zv = SegView{});
+                                const double *dinv = nullptr, SegView zv = SegView{}, const double *W = nullptr, int block = 1,
+                                long lda = 0);
 
 // ---- Jacobi -------------------------------------------------------------------------------------------
 // dst[i] = A(row0 + i, row0 + i) for the shard's rows (dst: its Ap slice, which the segment exchange then gathers).
@@ -149,6 +151,21 @@ hipError_t launch_diag_slice(const double *A, long lda, int rows, int row0, doub
 // From the gathered slices: dinv[c] = 1 / a_cc for c < n, 0 up to lda; *bad = min(*bad, first row whose a_cc is not finite and
 // > 0) (the caller sets *bad = INT_MAX before).
 hipError_t launch_jacobi_dinv(SegView apv, int n, long lda, double *dinv, int *bad, hipStream_t s);
+
+// ---- block Jacobi -------------------------------------------------------------------------------------
+// z = D_b^-1 r, D_b = the block x block diagonal blocks of A over the global ranges [j block, min((j+1) block, n)).  The inverses:
+// W[t * lda + i] = (D_b^-1)(i, s(i) + t), s(i) = i - i mod block; block x lda doubles per shard, replicated like dinv, zero
+// outside the truncated last block and in the pad rows.  launch_update_xr / launch_init_residual with W != nullptr run the
+// block forms: z_i = one fma chain from +0.0 over t ascending, the same in every kernel.
+constexpr int kBjMaxBlock = 256;   // every allowed block divides the 256 rows of an update workgroup
+constexpr int kBjLdsBlock = 128;   // up to here the inversion works on a copy of the block in LDS
+bool bj_block_ok(int block);       // 1, 2, 4, ..., kBjMaxBlock
+// Extraction: dst[y * dst_stride + i] = A(row0 + i, s(row0 + i) + t0 + y) for y < nt, i < rows; 0 where the column is >= n.
+hipError_t launch_bj_col_slice(const double *A, long lda, int n, int rows, int row0, int block, int t0, int nt, double *dst,
+                               long dst_stride, hipStream_t s);
+// Inversion in place, one workgroup per block, from the LOWER triangles (no pivoting; the result is mirrored: symmetric bit for
+// bit).  A pivot that is not finite and > 0: *bad = min(*bad, the block's first row).
+hipError_t launch_bj_invert(double *W, long lda, int n, int block, int *bad, hipStream_t s);
 
 // v_full[c] = segment value of column c (c < n), 0 for the pad: turns gathered slices into a replicated vector.
 hipError_t launch_unpack_segments(SegView seg, double *v_full, long lda, hipStream_t s);
@@ -257,6 +274,9 @@ long long lap2d_csr_nnz(int size, int row0, int rows);
 hipError_t launch_csr_generate_lap2d(long long *row_ptr, int *col, double *vals, int size, int row0, int rows, hipStream_t s);
 // Jacobi set-up: dst[i] = the stored entry (row0 + i, row0 + i), or 0 where the row has none.
 hipError_t launch_csr_diag_slice(const CsrView &cv, int rows, int row0, double *dst, hipStream_t s);
+// Block-Jacobi set-up: launch_bj_col_slice on CSR storage (an entry the row does not store is 0).
+hipError_t launch_csr_bj_col_slice(const CsrView &cv, int n, int rows, int row0, int block, int t0, int nt, double *dst,
+                                   long dst_stride, hipStream_t s);
 
 // ---- direct peer exchange (CGX_COMM_P2P): a lean all-gather over IPC-mapped mailboxes ---------------------
 // Every rank owns one fine-grained mailbox; all ranks map all mailboxes.  Layout (identical on every rank):

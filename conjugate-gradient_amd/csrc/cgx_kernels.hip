@@ -859,6 +859,276 @@ __global__ __launch_bounds__(256) void k_update_xr_strided_pc(int n, int rows, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// Block Jacobi: z = D_b^-1 r with the B x B diagonal blocks of A inverted once per matrix.
+// W[t * lda + i] = (D_b^-1)(i, s(i) + t), s(i) = i - i mod B: replicated like dinv, zero outside the (truncated last) block and in
+// the pad rows.  A workgroup of an update kernel owns 256 consecutive global rows starting at a multiple of 256, and B divides
+// 256, so a tile holds whole blocks: its 256 values of r_new go to LDS and thread i runs ONE fma chain from +0.0 over t = 0 ...
+// B-1 ascending, acc = fma(W[t][i], r_new[s(i) + t], acc) -- the same chain in every kernel below, so z_i depends on (i, B)
+// only.  (Terms beyond a truncated block are fma(0, 0, acc) = acc.)
+// ------------------------------------------------------------------------------------------------
+constexpr int kBjEarly = 16;   // W loads issued ahead of the first wait (they do not depend on alpha); the rest in steps of 8
+
+template <int B>
+struct BjEarly {
+    static constexpr int N = B < kBjEarly ? B : kBjEarly;
+    double w[N];
+};
+
+// the thread's first W entries; `row` is clamped by the caller to a row that exists (a pad row's z is never stored)
+template <int B>
+__device__ __forceinline__ BjEarly<B> bj_issue(const double *__restrict__ W, long lda, long row)
+{
+    BjEarly<B> e;
+#pragma unroll
+    for (int t = 0; t < BjEarly<B>::N; ++t) e.w[t] = W[(long)t * lda + row];
+    return e;
+}
+
+// z_i from the tile's r_new in LDS (rl[0 .. 256), written and barriered by the caller)
+template <int B>
+__device__ __forceinline__ double bj_chain(const BjEarly<B> &e, const double *__restrict__ W, long lda, long row, const double *rl)
+{
+    const double *rb = rl + ((int)threadIdx.x & ~(B - 1));   // the block's start inside the tile: an LDS broadcast per quarter wave
+    double acc = 0.0;
+#pragma unroll
+    for (int t = 0; t < BjEarly<B>::N; ++t) acc = fma(e.w[t], rb[t], acc);
+    if constexpr (B > kBjEarly) {
+        const double *wp = W + (long)kBjEarly * lda + row;
+#pragma unroll 1   // one running pointer: unrolled, the B - 16 row offsets t * lda spill scalar registers
+        for (int t0 = kBjEarly; t0 < B; t0 += 8, wp += 8 * lda) {
+            double w[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w[u] = wp[(long)u * lda];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc = fma(w[u], rb[t0 + u], acc);
+        }
+    }
+    return acc;
+}
+
+__device__ __forceinline__ PcRow bj_row(double r_new, double z)
+{
+    PcRow o;
+    o.r = r_new;
+    o.z = z;
+    o.rr = r_new * r_new;
+    o.rz = r_new * z;
+    return o;
+}
+
+// K3, block-Jacobi form of k_update_xr_pc: the same loads, the same alpha, the same partials; z from the chain above.
+template <int B>
+__global__ __launch_bounds__(256) void k_update_xr_bj(int n, int rows, int row0, const double *__restrict__ p_new, SegView apv,
+                                                       int tail_off, int tail_count, double *__restrict__ x, SegView rv, Scalars *sc,
+                                                       int parity, const double *__restrict__ W, long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    double *r = rv.base;
+    const int done = sc->done;
+    const double rsold = sc->rs[parity];
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    const int li = i - row0;
+    const bool in = i < n, own = in && li >= 0 && li < rows;
+    double ap_i = 0.0, r_i = 0.0, p_i = 0.0, x_i = 0.0;
+    if (in) { ap_i = seg_load(apv, i); r_i = r[i]; }
+    if (own) { p_i = p_new[i]; x_i = x[li]; }
+    const long wrow = in ? i : 0;
+    const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
+    double cs = 0.0;
+    {
+        const int total = apv.nranks * tail_count;
+        const double *tails = apv.base + apv.Sr + tail_off;
+        auto at = [&](int f) {
+            if (apv.nranks == 1) return tails[f];
+            const int q = f / tail_count;
+            return tails[(long)q * apv.S + (f - q * tail_count)];
+        };
+        for (int f = threadIdx.x; f < total; f += 4 * 256) {   // the plain kernel's order
+            double a[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int g = f + u * 256;
+                const double val = at(g < total ? g : total - 1);
+                a[u] = g < total ? val : 0.0;
+            }
+            cs += (a[0] + a[1]) + (a[2] + a[3]);
+        }
+    }
+    if (done) return;
+    const double conj = block_sum<4>(cs, lds);
+    const double alpha = safeguarded_alpha(rsold, conj);
+    const double rn = in ? fma(-alpha, ap_i, r_i) : 0.0;   // rows past n: exactly 0, they meet W's zeros only
+    rl[threadIdx.x] = rn;
+    __syncthreads();
+    const double z = bj_chain<B>(e, W, lda, wrow, rl);
+    double rr = 0.0, rz = 0.0;
+    if (in) {
+        const PcRow o = bj_row(rn, z);
+        r[i] = o.r;
+        zv.base[i] = o.z;
+        rr = o.rr;
+        rz = o.rz;
+    }
+    if (own) x[li] = fma(alpha, p_i, x_i);
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+}
+
+// The block form of k_update_xr_strided_pc (more than 256 * kMaxVectorGrid rows): the workgroups stride over whole tiles, so
+// that every barrier is reached by all 256 threads.
+template <int B>
+__global__ __launch_bounds__(256) void k_update_xr_strided_bj(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
+                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ W,
+                                                               long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    double *r = rv.base;
+    const int done = sc->done;
+    const double rsold = sc->rs[parity];
+    double cs = 0.0;
+    for (int q = 0; q < apv.nranks; ++q) {
+        const double *tail = apv.base + (long)q * apv.S + apv.Sr + tail_off;
+        for (int j = threadIdx.x; j < tail_count; j += 256) cs += tail[j];
+    }
+    if (done) return;
+    const double conj = block_sum<4>(cs, lds);
+    const double alpha = safeguarded_alpha(rsold, conj);
+    double rr = 0.0, rz = 0.0;
+    for (long base = (long)blockIdx.x * 256; base < n; base += (long)gridDim.x * 256) {
+        const long i = base + threadIdx.x;
+        const bool in = i < n;
+        const long wrow = in ? i : 0;
+        const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
+        const double rn = in ? fma(-alpha, seg_load(apv, (int)i), r[i]) : 0.0;
+        __syncthreads();   // the previous tile's chains have read rl
+        rl[threadIdx.x] = rn;
+        __syncthreads();
+        const double z = bj_chain<B>(e, W, lda, wrow, rl);
+        if (in) {
+            const PcRow o = bj_row(rn, z);
+            r[i] = o.r;
+            zv.base[i] = o.z;
+            rr += o.rr;
+            rz += o.rz;
+            const long li = i - row0;
+            if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);
+        }
+    }
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+}
+
+// Block-Jacobi set-up: r0 = b - A x0 as k_init_residual_pc, z0 = D_b^-1 r0 by the same chain.
+template <int B>
+__global__ __launch_bounds__(256) void k_init_residual_bj(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
+                                                           const double *__restrict__ W, long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    double *r = rv.base;
+    double rr = 0.0, rz = 0.0;
+    for (long base = (long)blockIdx.x * 256; base < n; base += (long)gridDim.x * 256) {
+        const long i = base + threadIdx.x;
+        const bool in = i < n;
+        const long wrow = in ? i : 0;
+        const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
+        const double rn = in ? b_full[i] - seg_load(apv, (int)i) : 0.0;
+        __syncthreads();
+        rl[threadIdx.x] = rn;
+        __syncthreads();
+        const double z = bj_chain<B>(e, W, lda, wrow, rl);
+        if (in) {
+            const PcRow o = bj_row(rn, z);
+            r[i] = o.r;
+            zv.base[i] = o.z;
+            rr += o.rr;
+            rz += o.rz;
+        }
+    }
+    rr = block_sum<4>(rr, lds);
+    rz = block_sum<4>(rz, lds);
+    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+}
+
+// Set-up, extraction: dst[y * dst_stride + i] = A(row0 + i, s(row0 + i) + t) for t = t0 + y (y = blockIdx.y), 0 where that column
+// lies past n (the truncated last block).  One rank: dst = W, dst_stride = lda, all t in one launch; several: dst = the shard's Ap
+// slice, one t per launch, gathered like the diagonal.
+__global__ __launch_bounds__(256) void k_bj_col_slice(const double *__restrict__ A, long lda, int n, int rows, int row0, int block,
+                                                       int t0, double *__restrict__ dst, long dst_stride)
+{
+    const int t = t0 + (int)blockIdx.y;
+    double *d = dst + (long)blockIdx.y * dst_stride;
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < rows; i += (long)gridDim.x * 256) {
+        const long g = row0 + i;
+        const long c = g - g % block + t;
+        d[i] = c < n ? A[i * lda + c] : 0.0;
+    }
+}
+
+// Set-up, inversion: one workgroup per block, in place in W (LDS_COPY: on a copy of the block in LDS, written back at the end).
+// Reads the LOWER triangle of the block only.  The symmetric sweep: for k = 0 ... m-1, with c = column k of the current
+// matrix and d = 1 / c_k:  a_kk = -d,  a_ik = c_i d,  a_ij = a_ij - (c_i d) c_j  (i, j != k) -- after m sweeps a = -D^-1.
+// No pivoting, no data-dependent order: scaling rows and columns of D by powers of two scales every intermediate exactly, so
+// the result is the scaled inverse bit for bit.  Every pivot c_k (a diagonal entry of a Schur complement: > 0 for an SPD
+// block) must be finite and > 0, else *bad = min(*bad, the block's first row) and W's block is left unspecified.
+// At the end the lower triangle is negated and mirrored: W is symmetric bit for bit.
+// a(i, j) for i >= j sits at a[j * ld + i]; thread th works on row th % block, columns th / block + u * (256 / block).
+template <bool LDS_COPY>
+__global__ __launch_bounds__(256) void k_bj_invert(double *W, long lda, int n, int block, int *bad)
+{
+    extern __shared__ double bj_lds[];   // column k [block] (+ LDS_COPY: the block, block x block)
+    const int s = (int)blockIdx.x * block;
+    const int m = (n - s) < block ? (n - s) : block;
+    const int th = (int)threadIdx.x;
+    double *col = bj_lds;
+    double *a = LDS_COPY ? bj_lds + block : W + s;
+    const long ld = LDS_COPY ? block : lda;
+    const int i = th & (block - 1), jg = th / block, jstep = 256 / block;
+    if (LDS_COPY) {
+        if (i < m)
+            for (int j = jg; j <= i; j += jstep) a[j * ld + i] = W[(long)j * lda + s + i];
+    }
+    bool ok = true;
+    for (int k = 0; k < m; ++k) {
+        __syncthreads();   // the previous sweep's stores
+        if (th < m) col[th] = th < k ? a[th * ld + k] : a[k * ld + th];
+        __syncthreads();
+        const double p = col[k];
+        if (!(p > 0.0 && p <= 1.7976931348623157e308)) {   // NaN, <= 0, +inf: the same for every thread
+            ok = false;
+            break;
+        }
+        const double d = 1.0 / p;
+        if (i < m) {
+            const double fi = col[i] * d;
+            for (int j = jg; j <= i; j += jstep) {
+                double v;
+                if (i == k) v = (j == k) ? -d : col[j] * d;
+                else if (j == k) v = fi;
+                else v = fma(-fi, col[j], a[j * ld + i]);
+                a[j * ld + i] = v;
+            }
+        }
+    }
+    if (!ok) {
+        if (th == 0) atomicMin(bad, s);
+        return;
+    }
+    __syncthreads();
+    if (i < m)
+        for (int j = jg; j <= i; j += jstep) {
+            const double v = -a[j * ld + i];
+            W[(long)j * lda + s + i] = v;
+            W[(long)i * lda + s + j] = v;
+        }
+}
+
+// ------------------------------------------------------------------------------------------------
 // Banded storage (opt-in fast path; NOT the reference's dense GEMV contract).
 // K1 on the diagonals of the row block: one thread per row, diagonals in ascending offset order (= ascending
 // column order), every load coalesced: vals[t][i..i+63] and p[g+off .. g+off+63].  Same head, same p_new, same
@@ -1342,8 +1612,28 @@ int update_xr_grid(int count)
 
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s, hipEvent_t e0,
-                            hipEvent_t e1, const double *dinv, SegView zv)
+                            hipEvent_t e1, const double *dinv, SegView zv, const double *W, int block, long lda)
 {
+    if (W) {   // block Jacobi (block > 1): the k_update_xr_bj family
+        const bool tile = (long)update_xr_grid(n) * 256 >= n;
+        const dim3 grid(update_xr_grid(n));
+#define CGX_BJ_UPDATE(BB)                                                                                                          \
+    case BB:                                                                                                                       \
+        if (tile)                                                                                                                  \
+            hipExtLaunchKernelGGL((k_update_xr_bj<BB>), grid, dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, tail_off,     \
+                                  tail_count, x, rv, sc, parity, W, lda, zv);                                                     \
+        else                                                                                                                       \
+            hipExtLaunchKernelGGL((k_update_xr_strided_bj<BB>), grid, dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,       \
+                                  tail_off, tail_count, x, rv, sc, parity, W, lda, zv);                                           \
+        break;
+        switch (block) {
+            CGX_BJ_UPDATE(2) CGX_BJ_UPDATE(4) CGX_BJ_UPDATE(8) CGX_BJ_UPDATE(16) CGX_BJ_UPDATE(32) CGX_BJ_UPDATE(64)
+            CGX_BJ_UPDATE(128) CGX_BJ_UPDATE(256)
+        default: return hipErrorInvalidValue;
+        }
+#undef CGX_BJ_UPDATE
+        return hipGetLastError();
+    }
     if (dinv) {
         if ((long)update_xr_grid(n) * 256 >= n)
             hipExtLaunchKernelGGL(k_update_xr_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,
@@ -1566,8 +1856,21 @@ hipError_t launch_solve_end(int n, const double *Ax, const double *b, const doub
 }
 
 hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
-                                const double *dinv, SegView zv)
+                                const double *dinv, SegView zv, const double *W, int block, long lda)
 {
+    if (W) {
+#define CGX_BJ_INIT(BB)                                                                                                            \
+    case BB:                                                                                                                       \
+        hipLaunchKernelGGL((k_init_residual_bj<BB>), dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, W, lda, zv);    \
+        break;
+        switch (block) {
+            CGX_BJ_INIT(2) CGX_BJ_INIT(4) CGX_BJ_INIT(8) CGX_BJ_INIT(16) CGX_BJ_INIT(32) CGX_BJ_INIT(64) CGX_BJ_INIT(128)
+            CGX_BJ_INIT(256)
+        default: return hipErrorInvalidValue;
+        }
+#undef CGX_BJ_INIT
+        return hipGetLastError();
+    }
     if (dinv) hipLaunchKernelGGL(k_init_residual_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, dinv, zv);
     else hipLaunchKernelGGL(k_init_residual, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, partials);
     return hipGetLastError();
@@ -1583,6 +1886,39 @@ hipError_t launch_diag_slice(const double *A, long lda, int rows, int row0, doub
 hipError_t launch_jacobi_dinv(SegView apv, int n, long lda, double *dinv, int *bad, hipStream_t s)
 {
     hipLaunchKernelGGL(k_jacobi_dinv, dim3(update_xr_grid((int)lda)), dim3(256), 0, s, apv, n, lda, dinv, bad);
+    return hipGetLastError();
+}
+
+bool bj_block_ok(int block)
+{
+    return block >= 1 && block <= kBjMaxBlock && (block & (block - 1)) == 0;
+}
+
+hipError_t launch_bj_col_slice(const double *A, long lda, int n, int rows, int row0, int block, int t0, int nt, double *dst,
+                               long dst_stride, hipStream_t s)
+{
+    if (rows <= 0) return hipSuccess;
+    int grid = ceil_div(rows, 256);
+    if (grid > 1024) grid = 1024;
+    hipLaunchKernelGGL(k_bj_col_slice, dim3(grid, nt), dim3(256), 0, s, A, lda, n, rows, row0, block, t0, dst, dst_stride);
+    return hipGetLastError();
+}
+
+hipError_t launch_bj_invert(double *W, long lda, int n, int block, int *bad, hipStream_t s)
+{
+    if (!bj_block_ok(block) || block < 2) return hipErrorInvalidValue;
+    const int nblocks = ceil_div(n, block);
+    if (block <= kBjLdsBlock) {   // the block fits in LDS beside column k: up to 129 KiB of the CU's 160
+        const size_t bytes = ((size_t)block * block + block) * sizeof(double);
+        if (bytes > 64 * 1024) {
+            const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void *>(k_bj_invert<true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+            if (e != hipSuccess) return e;
+        }
+        hipLaunchKernelGGL((k_bj_invert<true>), dim3(nblocks), dim3(256), bytes, s, W, lda, n, block, bad);
+    } else {                      // 256 x 256: 512 KiB, in place in W (it stays in L2)
+        hipLaunchKernelGGL((k_bj_invert<false>), dim3(nblocks), dim3(256), (size_t)block * sizeof(double), s, W, lda, n, block, bad);
+    }
     return hipGetLastError();
 }
 

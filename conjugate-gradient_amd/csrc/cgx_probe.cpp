@@ -319,6 +319,24 @@ cgx_status cgx_probe_get_source_term(cgx_ctx *ctx, int local_shard, double *b_ou
     return CGX_OK;
 }
 
+// TEST PROBE: the replicated block inverses of block Jacobi as n rows of `block` doubles: row i, entry t =
+// (D_b^-1)(i, s(i) + t).  Valid once a cgx_solve_begin with cgx_set_preconditioner_block > 1 has made them for the current matrix.
+cgx_status cgx_probe_get_precond_blocks(cgx_ctx *ctx, int local_shard, double *W_out)
+{
+    if (!ctx || !W_out || local_shard < 0 || local_shard >= (int)ctx->shards.size())
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_get_precond_blocks: bad argument");
+    const cgxi::Shard &s = ctx->shards[local_shard];
+    const int block = ctx->precond_block;
+    if (block <= 1 || !ctx->dinv_valid || !s.W || s.w_block != block)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_get_precond_blocks: no block inverses (needs a solve begun with a block size > 1)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<double> w((size_t)block * ctx->lda);
+    HIP_TRY(ctx, hipMemcpy(w.data(), s.W, w.size() * sizeof(double), hipMemcpyDeviceToHost));
+    for (long i = 0; i < ctx->n; ++i)
+        for (int t = 0; t < block; ++t) W_out[i * block + t] = w[(size_t)t * ctx->lda + i];
+    return CGX_OK;
+}
+
 // TEST PROBE: overwrite the dense row block of every local shard of the CURRENT problem with the hash matrix of
 // cgx_kernels.h (hash_entry): element (i, j) = a pure function of (seed, i, j) in [-1, 1), filled on the device.  The
 // geometry (n, partition, pitch, K1 plan) stays what the problem set before it defined; b and max_iter are untouched.

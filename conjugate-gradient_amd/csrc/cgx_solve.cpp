@@ -107,6 +107,75 @@ cgx_status gather_segments(cgx_ctx *ctx, bool with_tail)
 
 namespace cgxi {
 
+// ---- block-Jacobi set-up -----------------------------------------------------
+// Behind prepare_jacobi's refusals and buffers, once per matrix and block size: W (block x lda doubles per shard, replicated like
+// dinv).  For t = 0 ... block-1 every shard writes column t of its own block rows into its Ap slice, the segment exchange gathers
+// the slices as it gathers the diagonal, and every shard unpacks them into W's row t (one rank: one launch writes all of W).
+// Then every shard inverts every block from its gathered copy, on the device, so all ranks take the same decision, after the
+// last exchange.
+static cgx_status prepare_block_jacobi(cgx_ctx *ctx)
+{
+    const int block = ctx->precond_block;
+    if (ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange)
+        return fail(ctx, CGX_ERR_UNSUPPORTED,
+                    "block Jacobi: the update kernel with the peer exchange inside has no block form (p2p_separate_exchange = 1 has)");
+    hipStream_t st = ctx->stream;
+    const size_t wbytes = (size_t)block * (size_t)ctx->lda * sizeof(double);
+    for (auto &s : ctx->shards) {
+        if (s.W && s.w_block != block) {
+            ctx->dinv_valid = false;
+            HIP_TRY(ctx, hipFree(s.W));
+            s.W = nullptr;
+            s.w_block = 0;
+        }
+        if (!s.W) {
+            ctx->dinv_valid = false;
+            const hipError_t e = fault_due(ctx) ? hipErrorUnknown : hipMalloc(&s.W, wbytes);
+            if (e != hipSuccess) {
+                s.W = nullptr;
+                quiesce(ctx);
+                char msg[200];
+                snprintf(msg, sizeof msg, "block Jacobi: %zu bytes of block inverses (8 x block %d x pitch %ld) could not be allocated: %s",
+                         wbytes, block, ctx->lda, hipGetErrorString(e));
+                return fail(ctx, e == hipErrorOutOfMemory ? CGX_ERR_OOM : CGX_ERR_HIP, msg);
+            }
+            s.w_block = block;
+        }
+    }
+    if (ctx->dinv_valid) return CGX_OK;
+    const bool one = ctx->shards.size() == 1 && ctx->nranks == 1;
+    auto slice = [&](Shard &s, int t0, int nt, double *dst, long stride) -> cgx_status {
+        if (ctx->csr) HIP_TRY(ctx, cgx::launch_csr_bj_col_slice(s.csr, ctx->n, s.rows, s.row0, block, t0, nt, dst, stride, st));
+        else HIP_TRY(ctx, cgx::launch_bj_col_slice(s.A, ctx->lda, ctx->n, s.rows, s.row0, block, t0, nt, dst, stride, st));
+        return CGX_OK;
+    };
+    if (one) {
+        Shard &s = ctx->shards[0];
+        HIP_TRY(ctx, hipMemsetAsync(s.W, 0, wbytes, st));   // the pad rows
+        CGX_TRY(slice(s, 0, block, s.W, ctx->lda));
+    } else {
+        for (int t = 0; t < block; ++t) {
+            for (auto &s : ctx->shards) CGX_TRY(slice(s, t, 1, s.Ap(), 0));
+            CGX_TRY(gather_segments(ctx, false));
+            for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_unpack_segments(s.apv, s.W + (size_t)t * ctx->lda, ctx->lda, st));
+        }
+    }
+    if (!ctx->d_jbad) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_jbad), sizeof(int)));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_jbad, 0x7f, sizeof(int), st));   // 0x7f7f7f7f: above every row index
+    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_bj_invert(s.W, ctx->lda, ctx->n, block, ctx->d_jbad, st));
+    int bad = INT_MAX;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, ctx->d_jbad, sizeof(int), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    if (bad >= 0 && bad < ctx->n) {
+        char msg[200];
+        snprintf(msg, sizeof msg, "block Jacobi: the %d x %d diagonal block that begins at row %d is not positive definite "
+                                  "(a pivot of its factorisation is not finite and > 0)", block, block, bad);
+        return fail(ctx, CGX_ERR_BAD_ARG, msg);
+    }
+    ctx->dinv_valid = true;
+    return CGX_OK;
+}
+
 // ---- Jacobi set-up -----------------------------------------------------------
 // Collective, inside cgx_solve_begin: the refusals, the buffers, and -- once per matrix -- the diagonal.  Every shard reads the
 // diagonal of its own rows into its Ap slice, the transport's segment exchange gathers the slices, and every shard forms the
@@ -128,6 +197,7 @@ cgx_status prepare_jacobi(cgx_ctx *ctx)
         s.zv = s.rv;
         s.zv.base = s.zbuf;
     }
+    if (ctx->precond_block > 1) return prepare_block_jacobi(ctx);
     if (ctx->dinv_valid) return CGX_OK;
     for (auto &s : ctx->shards) {
         if (ctx->csr)   // the entry with col == row, 0 where the row has none (then refused below like any entry <= 0)
@@ -304,6 +374,7 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
 {
     hipStream_t st = ctx->stream;
     const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
+    const bool bj = pc && ctx->precond_block > 1;   // block Jacobi: the update kernel's block form (never with the exchange inside)
     // tail of iteration k-1 (cg.cc:117-132) + GEMV and p.Ap partials of iteration k (cg.cc:100-105)
     for (auto &s : ctx->shards) CGX_TRY(run_gemv_fused(ctx, s, k));
     if (ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange) {
@@ -334,7 +405,7 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
         const int count = folded ? 1 : (s.plan.variant == 6 ? cgx::plan_partials(s.plan) : ctx->npart);
         HIP_TRY(ctx, cgx::launch_update_xr(ctx->n, s.rows, s.row0, s.p[(k + 1) & 1], s.apv, folded ? ctx->npart : 0,
                                            count, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1,   // cg.cc:105-116
-                                           pc ? s.dinv : nullptr, s.zv));
+                                           pc ? s.dinv : nullptr, s.zv, bj ? s.W : nullptr, ctx->precond_block, ctx->lda));
     }
     return CGX_OK;
 }
@@ -616,7 +687,8 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
     CGX_TRY(gather_segments(ctx, false));
     for (auto &s : ctx->shards)
         HIP_TRY(ctx, cgx::launch_init_residual(n, s.b_full, s.apv, s.rv, s.partials, st,            // cg.cc:82 (Jacobi: and z0)
-                                               pc ? s.dinv : nullptr, s.zv));
+                                               pc ? s.dinv : nullptr, s.zv, pc && ctx->precond_block > 1 ? s.W : nullptr,
+                                               ctx->precond_block, ctx->lda));
     for (auto &s : ctx->shards) {
         // p_old of iteration 0 is 0, so K1(0) forms p = r + 0*0 = r  (p_sub = r_sub, cg.cc:85; Jacobi: p0 = z0)
         HIP_TRY(ctx, hipMemsetAsync(s.p[0], 0, vec_bytes, st));

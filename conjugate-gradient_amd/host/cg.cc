@@ -38,6 +38,7 @@ void CGSolver::set_max_iter(int maxIter) { check(cgx_set_max_iter(m_ctx, maxIter
 void CGSolver::tolerance(double tolerance) { check(cgx_set_tolerance(m_ctx, tolerance), "tolerance"); }
 
 void CGSolver::set_preconditioner(int kind) { check(cgx_set_preconditioner(m_ctx, kind), "set_preconditioner"); }
+void CGSolver::set_preconditioner_block(int block) { check(cgx_set_preconditioner_block(m_ctx, block), "set_preconditioner_block"); }
 
 int CGSolver::m() const
 {

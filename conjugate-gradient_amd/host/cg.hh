@@ -47,6 +47,7 @@ public:
     // additions
     /// CGX_PRECOND_NONE or CGX_PRECOND_JACOBI (include/cgx.h): takes effect at the next solve
     void set_preconditioner(int kind);
+    void set_preconditioner_block(int block);   // 1 = point Jacobi; 2 ... 256 = block Jacobi (cgx_set_preconditioner_block)
     const cgx_result &last_result() const { return m_result; }
     int rank() const { return m_cfg.rank; }
     int psize() const { return m_cfg.nranks; }

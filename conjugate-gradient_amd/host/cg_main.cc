@@ -15,6 +15,8 @@
 // output, a CSR mat-vec instead of the dense GEMV.  Not together with --banded.
 // `--jacobi` (NOT a reference mode) solves with the Jacobi preconditioner (include/cgx.h cgx_set_preconditioner): same stopping
 // test on sqrt(r.r) and the same output, usually fewer iterations on a matrix whose diagonal varies.
+// `--jacobi-block B` (implies --jacobi) inverts the B x B diagonal blocks instead of the diagonal entries (B = 1, 2, 4, ..., 256;
+// include/cgx.h cgx_set_preconditioner_block).
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -139,6 +141,8 @@ int usage(const char *prog)
               << "                                  not together with --banded)\n"
               << "         --jacobi                 opt-in, not in the reference: Jacobi-preconditioned CG (z = D^-1 r; stops on\n"
               << "                                  sqrt(r.r) < tol as without it; dense or CSR storage, per-launch loop)\n"
+              << "         --jacobi-block B         implies --jacobi: block Jacobi with the B x B diagonal blocks, B = 1, 2, 4,\n"
+              << "                                  ..., 256 (1 = --jacobi; not with --transport p2p)\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -157,6 +161,7 @@ int main(int argc, char **argv)
     bool stats = false, same_device = false, banded = false, csr = false, jacobi = false;
     std::string transport = "auto";
     std::string test_hang;   // --test-hang-stage
+    int jacobi_block = 1;
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -168,6 +173,10 @@ int main(int argc, char **argv)
         else if (a == "--banded") banded = true;
         else if (a == "--csr") csr = true;
         else if (a == "--jacobi") jacobi = true;
+        else if (a == "--jacobi-block" && i + 1 < argc) {
+            jacobi = true;
+            jacobi_block = atoi(argv[++i]);
+        }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -396,6 +405,7 @@ int main(int argc, char **argv)
         const int psize = cfg.nranks;
         CGSolver &solver = *holder;
         if (jacobi) solver.set_preconditioner(CGX_PRECOND_JACOBI);   // every rank, before the first solve
+        if (jacobi_block != 1) solver.set_preconditioner_block(jacobi_block);
 
         if (gen_form) solver.generate_lap2d_matrix(gen_n);   // cg_main.cc:31
         else solver.read_matrix(pos[0]);                     // code/CUDA/cg_main.cc:37
@@ -451,6 +461,7 @@ int main(int argc, char **argv)
                 }
                 std::cerr << " persistent_launches_redone_per_launch=" << rec[8];
                 if (jacobi) std::cerr << " precond=jacobi";   // only when set: the plain line stays as it was
+                if (jacobi_block != 1) std::cerr << " block=" << jacobi_block;
                 std::cerr << std::endl;
             }
         }

@@ -258,6 +258,21 @@ cgx_status  cgx_get_size(const cgx_ctx *ctx, int *m, int *n);   /* CGSolver::m()
 #define CGX_PRECOND_JACOBI 1
 cgx_status  cgx_set_preconditioner(cgx_ctx *ctx, int kind);
 cgx_status  cgx_get_preconditioner(const cgx_ctx *ctx, int *kind);
+/* The block size of CGX_PRECOND_JACOBI: block = 1 (the default) is the point Jacobi above, exactly its
+ * kernels and bits; block in {2, 4, 8, 16, 32, 64, 128, 256} is block Jacobi, z = D_b^-1 r with D_b = the block x block diagonal
+ * blocks of A as stored, over the global index ranges [j block, min((j+1) block, n)) (shard boundaries do not cut them).
+ * z_i is one fma chain over the block's entries in ascending order, so it depends on (i, block) only, not on the shard count or
+ * the transport.  Anything else, or a call between cgx_solve_begin and cgx_solve_end: CGX_ERR_BAD_ARG.  The setting belongs to
+ * the context, survives new matrices, starts no GPU work, takes effect at the next begin and is used only while the kind is
+ * CGX_PRECOND_JACOBI (every rank passes the same block).  That begin extracts, gathers and inverts the blocks on the device once
+ * per matrix and block size (from each block's lower triangle, no pivoting); a block that is not positive definite gives
+ * CGX_ERR_BAD_ARG on every rank (its first row in cgx_last_error) and leaves the context usable.  The inverses take
+ * 8 * block * lda bytes of device memory per shard (lda = the row pitch, >= n): 1 GiB at n = 2^24 with block 8; a failed
+ * allocation is CGX_ERR_OOM.  Refused like point Jacobi (banded storage, cgx_solve_multi, gemv_variant 40000 / 50000), and with
+ * block > 1 also CGX_COMM_P2P with the exchange folded into the update kernel: CGX_ERR_UNSUPPORTED at cgx_solve_begin
+ * (p2p_separate_exchange = 1 is supported). */
+cgx_status  cgx_set_preconditioner_block(cgx_ctx *ctx, int block);
+cgx_status  cgx_get_preconditioner_block(const cgx_ctx *ctx, int *block);
 /* Storage of local shard `local_shard`: *format = cgx_matrix_format; banded: *ndiag and offsets[0..*ndiag)
  * (column minus row, ascending; room for CGX_MAX_DIAGONALS ints or NULL); *matrix_bytes = device bytes of the block. */
 cgx_status  cgx_get_matrix_format(const cgx_ctx *ctx, int local_shard, int *format, int *ndiag, int *offsets,
@@ -368,6 +383,10 @@ cgx_status  cgx_probe_get_source_term(cgx_ctx *ctx, int local_shard, double *b_o
  * (csrc/cgx_kernels.h hash_entry; the parity tests restate it so that a checker rebuilds any row on the host).
  * symmetric != 0: (i,j) and (j,i) share the value of (min, max).  diag != 0: A(i,i) = diag. */
 cgx_status  cgx_probe_fill_matrix_hash(cgx_ctx *ctx, unsigned long long seed, int symmetric, double diag);
+/* TEST ONLY: the replicated block inverses of local shard `local_shard` as n rows of `block` doubles: row i, entry t =
+ * (D_b^-1)(i, s(i) + t) with s(i) = i - i mod block (0 outside a truncated last block).  Valid after a cgx_solve_begin with a
+ * block size > 1; otherwise CGX_ERR_BAD_ARG. */
+cgx_status  cgx_probe_get_precond_blocks(cgx_ctx *ctx, int local_shard, double *W_out);
 /* Copy this shard's device row block (rows x n, dense, row-major) back to the host (banded storage is expanded). */
 cgx_status  cgx_probe_get_matrix_rows(cgx_ctx *ctx, int local_shard, double *A_out, int *row0, int *rows);
 
