@@ -33,12 +33,13 @@ EXPORTS = [
     "cgx_probe_get_source_term", "cgx_probe_set_fault_after", "cgx_probe_set_resident_limit", "cgx_probe_persistent_plan",
     "cgx_probe_parse_matrix_market", "cgx_probe_p2p_mailbox_to_host", "cgx_probe_fill_matrix_hash",
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
-    "cgx_solve_multi", "cgx_probe_gemv_multi",
+    "cgx_solve_multi", "cgx_probe_gemv_multi", "cgx_solve_shifted",
     "cgx_set_preconditioner", "cgx_get_preconditioner",
     "cgx_set_preconditioner_block", "cgx_get_preconditioner_block", "cgx_probe_get_precond_blocks",
     "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
+MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 _PRECOND_NAMES = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI}
 PRECOND_BLOCKS = (1, 2, 4, 8, 16, 32, 64, 128, 256)   # cgx_set_preconditioner_block
@@ -152,6 +153,7 @@ def lib():
         L.cgx_probe_resident_test.argtypes = [vp, C.c_ulonglong, C.c_int]
         L.cgx_probe_get_p2p_epoch.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
         L.cgx_solve_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_solve_shifted.argtypes = [vp, C.c_int, dp, dp, C.c_long, C.POINTER(Result)]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
         L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
@@ -420,6 +422,17 @@ class CGSolver:
         k = B.shape[0]
         res = (Result * max(k, 1))()
         self._check(lib().cgx_solve_multi(self._h, int(k), _dp(B), int(B.shape[1]), _dp(X), int(X.shape[1]), res))
+        return X, [res[j].as_dict() for j in range(k)]
+
+    def solve_shifted(self, shifts):
+        """shifts: sigma_j >= 0 (at most MAX_SHIFTS).  Returns (X, [result dicts]), X of shape (len(shifts), n): row j solves
+        (A + sigma_j I) x = b for the current matrix and source term from a zero guess, all shifts in one Krylov sequence with
+        one pass over A per iteration (multi-shift CG, cgx_solve_shifted)."""
+        sig = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        k, n = sig.size, self.n()
+        X = np.zeros((k, n), dtype=np.float64)
+        res = (Result * max(k, 1))()
+        self._check(lib().cgx_solve_shifted(self._h, int(k), _dp(sig), _dp(X), int(n), res))
         return X, [res[j].as_dict() for j in range(k)]
 
     def probe_gemv_multi(self, P):

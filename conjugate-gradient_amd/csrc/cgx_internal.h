@@ -172,6 +172,10 @@ struct cgx_ctx {
     // partials and scalars of the multi kernels, apart from the single path's buffers; made on first use, freed with the problem
     double *multi = nullptr;
     size_t multi_bytes = 0;
+    // multi-shift CG (cgx_solve_shifted, cgx_shift_host.cpp): ONE device block holding the kMaxShifts-wide x and p of the shifts, the
+    // block of the final verification and the shift scalars; made on first use, freed with the problem
+    double *shift = nullptr;
+    size_t shift_bytes = 0;
 
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 
@@ -298,6 +302,7 @@ cgx_status p2p_allgather(cgx_ctx *ctx, int chan, const double *src, int count, d
 cgx_status gather_scalars(cgx_ctx *ctx);
 cgx_status gather_segments(cgx_ctx *ctx, bool with_tail);
 cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full);
+cgx_status enqueue_iteration(cgx_ctx *ctx, int k);          // one body of the loop cg.cc:96-137: K1 fused, the exchange, K3
 cgx_status check_p2p_error(cgx_ctx *ctx);
 cgx_status resident_steps(cgx_ctx *ctx, int nsteps, int *redo);
 void reset_gemv_stats(cgx_ctx *ctx);

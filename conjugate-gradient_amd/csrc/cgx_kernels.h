@@ -463,4 +463,50 @@ hipError_t launch_multi_close(MultiScalars *ms, const double *rrp, int n, int nr
 hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const double *b, const double *x, MultiScalars *ms,
                               hipStream_t s);
 
+// ---- multi-shift CG: (A + sigma_j I) x_j = b for up to kMaxShifts shifts from one Krylov sequence (cgx_shift.hip) -------------
+// The seed is the single path's loop on A (K1 + K3, untouched); one kernel behind each K3 advances every shift.  X and P (the
+// x and p of the shifts) are column-major at pitch lda like the multi block: shift j at base + j * lda, zero padded up to lda.
+constexpr int kMaxShifts = 16;                 // = CGX_MAX_SHIFTS
+constexpr int kShiftLive = 0x7fffffff;         // frozen_at / all_at of a shift / a solve that is still running
+struct ShiftScalars {
+    double sigma[kMaxShifts];
+    double zeta[3][kMaxShifts];    // zeta_m of shift j at zeta[(m + 1) % 3][j]: the launch of iteration k reads m = k, k - 1 and
+                                   // writes m = k + 1, so no workgroup reads a slot another one of the same launch writes
+    double alpha[3], beta[3];      // the seed's alpha_m, beta_m at [(m + 1) % 3] (alpha_-1 = 1, beta_-1 = 0)
+    double res_last[kMaxShifts];   // |zeta_(k+1)| sqrt(r_(k+1).r_(k+1)) of the shift's last iteration k
+    double res_prev[kMaxShifts];   // |zeta_k| sqrt(r_k.r_k)
+    double norms[kMaxShifts][3];   // ||(A + sigma I) x - b||^2, ||b||^2, ||x||^2 (launch_shift_norms)
+    int    frozen_at[kMaxShifts];  // the iteration that froze the shift (kShiftLive: running).  An iteration number, not a flag:
+                                   // workgroup 0 of launch k writes k while the others still read, and both values mean "runs in k"
+    int    all_at;                 // the iteration that ended the loop (every shift frozen, or the seed broke); launches of later
+                                   // iterations exit at once
+    int    pad[3];
+};
+struct ShiftArgs {
+    int n, nshift;
+    long lda;
+    const double *r;               // the seed's r behind K3 of iteration k: r_(k+1)
+    const double *rrp;             // K3's r.r partials (the tail of the replicated r), folded as the next K1's head folds them
+    int nrr;
+    const double *pap;             // K1's p.Ap partials as K3 was handed them (tail offset and count), folded in K3's order
+    int npap;
+    int pap_strided;               // 1 = K3 ran in its strided form (more than 256 * kMaxVectorGrid rows): that form's fold order
+    Scalars *sc;                   // the seed's scalar block: rs[k & 1] = rsold of iteration k; done / k_final are raised when the
+                                   // loop ends, so that the seed's later kernels drain and the host's poll sees it
+    ShiftScalars *ss;
+    double *X, *P;
+    int k;
+    double tol;
+};
+// x_j = 0, p_j = b (zero padded up to lda) for j < nshift, and the scalar block set for iteration 0 (sigma: host array).
+hipError_t launch_shift_begin(int n, long lda, int nshift, const double *sigma, const double *b, double *X, double *P, ShiftScalars *ss,
+                              hipStream_t s);
+// Behind K3 of iteration k: alpha_k and beta_k refolded, zeta advanced, x_j and p_j updated, freeze and loop end decided.
+hipError_t launch_shift_update(const ShiftArgs &a, hipStream_t s);
+// The loop ran out after k iterations: residual_prev of the shifts still running (k == 0: sqrt(r0.r0) from the partials).
+hipError_t launch_shift_close(ShiftScalars *ss, const double *rrp, int nrr, int nshift, int k, hipStream_t s);
+// norms[j] = ||Y_j + sigma_j x_j - b||^2, ||b||^2, ||x_j||^2 with Y_j = A x_j, one workgroup per shift, fixed order.
+hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, const double *b, const double *X, ShiftScalars *ss,
+                              hipStream_t s);
+
 }  // namespace cgx

@@ -48,6 +48,10 @@ public:
     /// CGX_PRECOND_NONE or CGX_PRECOND_JACOBI (include/cgx.h): takes effect at the next solve
     void set_preconditioner(int kind);
     void set_preconditioner_block(int block);   // 1 = point Jacobi; 2 ... 256 = block Jacobi (cgx_set_preconditioner_block)
+    /// multi-shift CG (include/cgx.h cgx_solve_shifted): X[j * n() + i] = solution i of (A + shifts[j] I) x = b from a zero guess,
+    /// one pass over A per iteration for all shifts; the per-shift results are kept (shift_results), last_result() is shift 0's
+    void solve_shifted(const std::vector<double> &shifts, std::vector<double> &X);
+    const std::vector<cgx_result> &shift_results() const { return m_shift_results; }
     const cgx_result &last_result() const { return m_result; }
     int rank() const { return m_cfg.rank; }
     int psize() const { return m_cfg.nranks; }
@@ -61,6 +65,7 @@ private:
     cgx_ctx *m_ctx{nullptr};
     cgx_config m_cfg{};
     cgx_result m_result{};
+    std::vector<cgx_result> m_shift_results;
     bool m_verbose{true};
 };
 

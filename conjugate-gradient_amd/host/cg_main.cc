@@ -17,6 +17,9 @@
 // test on sqrt(r.r) and the same output, usually fewer iterations on a matrix whose diagonal varies.
 // `--jacobi-block B` (implies --jacobi) inverts the B x B diagonal blocks instead of the diagonal entries (B = 1, 2, 4, ..., 256;
 // include/cgx.h cgx_set_preconditioner_block).
+// `--shifts s0,s1,...` (NOT a reference mode) runs multi-shift CG instead of the plain solve (include/cgx.h cgx_solve_shifted): the
+// systems (A + s_j I) x = b for up to 16 shifts s_j >= 0 from one Krylov sequence, one pass over A per iteration.  The timing line
+// in OUTFILE is written as ever; one line per shift follows on stdout.  One GPU, dense or --csr, no --jacobi.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -143,6 +146,9 @@ int usage(const char *prog)
               << "                                  sqrt(r.r) < tol as without it; dense or CSR storage, per-launch loop)\n"
               << "         --jacobi-block B         implies --jacobi: block Jacobi with the B x B diagonal blocks, B = 1, 2, 4,\n"
               << "                                  ..., 256 (1 = --jacobi; not with --transport p2p)\n"
+              << "         --shifts s0,s1,...       opt-in, not in the reference: solve (A + s I) x = b for up to 16 shifts s >= 0 in\n"
+              << "                                  one Krylov sequence (multi-shift CG) instead of the plain solve; one GPU, dense\n"
+              << "                                  or --csr, not with --jacobi; prints one line per shift\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -162,6 +168,8 @@ int main(int argc, char **argv)
     std::string transport = "auto";
     std::string test_hang;   // --test-hang-stage
     int jacobi_block = 1;
+    std::vector<double> shifts;
+    bool shifted = false;
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -176,6 +184,20 @@ int main(int argc, char **argv)
         else if (a == "--jacobi-block" && i + 1 < argc) {
             jacobi = true;
             jacobi_block = atoi(argv[++i]);
+        }
+        else if (a == "--shifts" && i + 1 < argc) {
+            shifted = true;
+            std::stringstream list(argv[++i]);
+            std::string item;
+            while (std::getline(list, item, ',')) {
+                char *end = nullptr;
+                const double v = strtod(item.c_str(), &end);
+                if (item.empty() || *end != '\0') {
+                    std::cerr << argv[0] << ": --shifts takes a comma-separated list of numbers, not '" << item << "'\n";
+                    return usage(argv[0]);
+                }
+                shifts.push_back(v);
+            }
         }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
@@ -416,7 +438,9 @@ int main(int argc, char **argv)
         std::vector<double> x_d(static_cast<size_t>(n), 0.);   // cg_main.cc:49-50
 
         auto t1 = clk::now();                                // only solve() is timed, cg_main.cc:53-55
-        if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
+        std::vector<double> x_shifted;                       // --shifts: one solution per shift
+        if (shifted) solver.solve_shifted(shifts, x_shifted);
+        else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
         else solver.solve(x_d);
         second elapsed = clk::now() - t1;
 
@@ -427,6 +451,13 @@ int main(int argc, char **argv)
             } else {
                 std::cout << "Time for CG (dense solver)  = " << elapsed.count() << " [s]\n";   // code/CUDA/cg_main.cc:54
                 outfile << legacy_nt << "," << legacy_bw << "," << elapsed.count() << std::endl;   // :59
+            }
+            if (shifted) {
+                const std::vector<cgx_result> &sr = solver.shift_results();
+                for (size_t j = 0; j < sr.size(); ++j)
+                    std::cout << "\t[SHIFT " << shifts[j] << "] iterations = " << sr[j].iterations << ", converged = " << sr[j].converged
+                              << ", residual = " << std::scientific << sr[j].residual_prev << ", ||(A + sI)x - b||/||b|| = "
+                              << sr[j].rel_residual << std::defaultfloat << std::endl;
             }
             if (stats) {
                 const cgx_result &r = solver.last_result();

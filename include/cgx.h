@@ -318,6 +318,29 @@ cgx_status  cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, d
  * in ascending order.  P, Y host arrays, one vector per row (P[j*ldp + i]); pAp: nrhs doubles.  Same scope as cgx_solve_multi. */
 cgx_status  cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long ldp, double *Y, long ldy, double *pAp);
 
+/* ---- one right-hand side against a family of shifted matrices (one pass over A per iteration serves all shifts) ---- */
+/* Multi-shift CG: (A + sigma[j] I) x_j = b for nshift shifts sigma[j] >= 0, from ONE Krylov sequence.  The
+ * seed is cgx_solve's recurrence on A itself from x0 = 0 on the per-launch path (K1 + K3 per iteration, any per-launch plan, also
+ * where the context's plan is a persistent kernel: that plan is left as it is and the next cgx_solve uses it again); the residual
+ * of shift j stays zeta_j r, so every shift costs a scalar recurrence and two vector updates per iteration (csrc/cgx_shift.hip).
+ * Inputs: the current matrix and source term, cgx_set_tolerance / cgx_set_max_iter.  The initial guess is zero for every shift
+ * (the shifted residuals are collinear only from one common r0 = b): X is output only, one solution per ROW, X[j*ldx + i].
+ * Shift j is frozen in iteration k -- converged = 1, iterations = k, nothing writes its x afterwards -- when |zeta_j| sqrt(r.r)
+ * < tol, or when |zeta_j| < 2^-500 or is not finite (converged beyond what a double holds).  The loop ends, decided on the device
+ * and found by the check_every poll, when the seed breaks in iteration k (every shift still running is then converged at k), when
+ * every shift is frozen (the seed need not have converged), or after max_iter iterations (the shifts still running: converged =
+ * 0, iterations = max_iter).  res: nshift results (may be NULL): residual_last / residual_prev = |zeta| sqrt(r.r) of the last /
+ * previous iteration, x_norm = ||x_j||, rel_residual = the true ||(A + sigma_j I) x_j - b|| / ||b|| from a final mat-vec,
+ * seconds_* and gemv_* as cgx_solve_multi fills them, gemv_bytes that of the single K1.  The result of shift j depends on
+ * (A, b, sigma_j, tol, max_iter) only: not on the other shifts, their number or order, or check_every; shifts may repeat.
+ * sigma = 0 gives the bits of cgx_solve from a zero guess on the per-launch path.
+ * One GPU (CGX_COMM_SELF), dense or CSR storage.  CGX_ERR_UNSUPPORTED: more than one rank or CGX_COMM_LOOPBACK, banded storage,
+ * a preconditioner set (it breaks the collinearity), gemv_variant 40000 / 50000.  CGX_ERR_BAD_ARG: a null pointer, nshift outside
+ * 1 .. CGX_MAX_SHIFTS, ldx < n, a shift that is negative or not finite (its index in cgx_last_error), no matrix or no source
+ * term, an open cgx_solve_begin / cgx_solve_end pair.  A failed call leaves the context usable. */
+#define CGX_MAX_SHIFTS 16
+cgx_status  cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res);
+
 /* ---- kernel probes (parity tests of the individual hot ops through the C ABI) ------------- */
 /* Ap = A_shard * p  (K1; cblas_dgemv at cg.cc:101-102) for every local shard; y receives the n
  * results in global row order (LOOPBACK/SELF) or this rank's rows at their global offset (RCCL);
