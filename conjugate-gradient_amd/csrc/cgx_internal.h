@@ -6,6 +6,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -168,7 +169,7 @@ struct cgx_ctx {
     bool steps_ev_pending = false;
     double steps_device_ms = 0;
 
-    // several right-hand sides (cgx_solve_multi, cgx_multi.cpp): ONE device block holding kMaxRhs-wide B, X, R, P[2], Y and the
+    // several right-hand sides (cgx_solve_multi, cgx_multi_host.cpp): ONE device block holding kMaxRhs-wide B, X, R, P[2], Y and the
     // partials and scalars of the multi kernels, apart from the single path's buffers; made on first use, freed with the problem
     double *multi = nullptr;
     size_t multi_bytes = 0;
@@ -296,7 +297,10 @@ struct MtxEntries {
 cgx_status parse_matrix_market(const char *path, MtxEntries *out, std::string *err, int nthreads, bool header_only = false);
 int default_parse_threads();   // CGX_MTX_THREADS, else the host's hardware threads, at most 16
 
-// cgx_solve.cpp
+// cgx_precond.cpp
+cgx_status prepare_jacobi(cgx_ctx *ctx);   // inside cgx_solve_begin: refusals, buffers, and once per matrix dinv or the block inverses
+
+// cgx_solve.cpp: the exchanges, one iteration, the persistent launches
 cgx_status p2p_allgather(cgx_ctx *ctx, int chan, const double *src, int count, double *dst, long dst_stride, int copy_self,
                          int tail_off = 0, int tail_n = 0, int sum_off = 0);
 cgx_status gather_scalars(cgx_ctx *ctx);
@@ -305,8 +309,81 @@ cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full);
 cgx_status enqueue_iteration(cgx_ctx *ctx, int k);          // one body of the loop cg.cc:96-137: K1 fused, the exchange, K3
 cgx_status check_p2p_error(cgx_ctx *ctx);
 cgx_status resident_steps(cgx_ctx *ctx, int nsteps, int *redo);
+// cgx_solve.cpp: what cgx_solve_steps / _end, cgx_solve_multi and cgx_solve_shifted share (and run_polled below)
 void reset_gemv_stats(cgx_ctx *ctx);
-cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out);      // an event of the K1 timing pool
+// The timing decision of the next K1 launch of a steps call: an event pair to bracket it with, or two nulls.
+cgx_status next_gemv_events(cgx_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1);
 cgx_status harvest_gemv_events(cgx_ctx *ctx);              // fold the recorded pairs into the K1 statistics (after a sync)
+void fill_k1_stats(const cgx_ctx *ctx, cgx_result *res);   // launches, avg / min / max / median, discarded, steps_device_ms
+double one_gpu_gemv_bytes(const cgx_ctx *ctx);             // algorithmic bytes of one K1 launch of shard 0: dense, CSR or banded
+// The refusals every one-GPU entry point begins with, in this order: no context (no message), no problem, an open begin / end
+// pair, more than one GPU.
+cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn);
+// A side block of the context (cgx_ctx::multi, cgx_ctx::shift): allocated and zeroed on first use, freed again if that fails.
+cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes);
+
+// Lays a side block out in 128-byte aligned pieces; base == nullptr only measures (bytes()).
+struct Carver {
+    double *base;
+    size_t off = 0;
+    double *take(size_t count)
+    {
+        double *p = base ? base + off : nullptr;
+        off += (count + 15) / 16 * 16;
+        return p;
+    }
+    template <class T>
+    T *take_struct() { return reinterpret_cast<T *>(take((sizeof(T) + 7) / 8)); }
+    size_t bytes() const { return off * sizeof(double); }
+};
+
+// p.Ap partials per column that any multi-vector K1 launch may write: the largest K1m grid over the widths
+inline int k1p_stride(int n)
+{
+    int g = 0;
+    for (int w = 1; w <= cgx::kMaxRhs; w *= 2) g = std::max(g, cgx::multi_gemv_grid(n, w));
+    return g;
+}
+
+// THE polled host loop of every solve on the per-launch kernels: up to `count` calls of enqueue_one(i), i = 0, 1, ..., in batches
+// of cfg.check_every (made positive by cgx_create).  Behind each batch the two flag words at d_flags ({done, k_final} or their
+// like) are copied into a pinned slot and an event is recorded; then the host waits for the batch BEFORE it, so one batch stays
+// queued, and stops at a raised first word.  window: markers on the stream in front of the first and behind the last kernel
+// (steps_ev, read by harvest_gemv_events).  *enqueued: the iterations of the batches that were enqueued completely.  The body is
+// a template parameter so that it is inlined: at small n this loop is the host's hot path.
+template <class Body>
+cgx_status run_polled(cgx_ctx *ctx, const int *d_flags, int count, bool window, Body &&enqueue_one, int *enqueued)
+{
+    hipStream_t st = ctx->stream;
+    *enqueued = 0;
+    if (window) {
+        for (auto &e : ctx->steps_ev)
+            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
+        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[0], st));
+    }
+    const int every = ctx->cfg.check_every;
+    int k = 0, slot = 0;
+    bool pending[2] = {false, false}, stop = false;
+    while (k < count && !stop) {
+        const int batch = std::min(count - k, every);
+        for (int i = 0; i < batch; ++i) CGX_TRY(enqueue_one(k + i));
+        k += batch;
+        *enqueued = k;
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags + 2 * slot, d_flags, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
+        HIP_TRY(ctx, hipEventRecord(ctx->flag_ev[slot], st));
+        pending[slot] = true;
+        slot ^= 1;
+        if (pending[slot]) {
+            HIP_TRY(ctx, hipEventSynchronize(ctx->flag_ev[slot]));
+            pending[slot] = false;
+            if (ctx->h_flags[2 * slot]) stop = true;   // identical on every rank: rsnew is bit-identical (cg.cc:117-121)
+        }
+    }
+    if (window) {   // (a stop marker is only ever paired with the start marker of the same call)
+        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[1], st));
+        ctx->steps_ev_pending = true;
+    }
+    return CGX_OK;
+}
 
 }  // namespace cgxi

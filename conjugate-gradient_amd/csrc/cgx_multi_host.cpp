@@ -24,43 +24,27 @@ struct MultiView {
     cgx::MultiScalars *ms;
 };
 
-int k1p_stride(int n)   // the largest K1m grid over the widths
-{
-    int g = 0;
-    for (int w = 1; w <= kW; w *= 2) g = std::max(g, cgx::multi_gemv_grid(n, w));
-    return g;
-}
-
 size_t multi_layout(const cgx_ctx *ctx, double *base, MultiView *v)
 {
     const size_t vec = (size_t)kW * ctx->lda;
-    size_t off = 0;
-    auto take = [&](size_t count) {
-        double *p = base ? base + off : nullptr;
-        off += (count + 15) / 16 * 16;   // 128-B aligned pieces
-        return p;
-    };
-    v->B = take(vec);
-    v->X = take(vec);
-    v->R = take(vec);
-    v->P[0] = take(vec);
-    v->P[1] = take(vec);
-    v->Y = take(vec);
-    v->k1p = take((size_t)kW * k1p_stride(ctx->n));
-    v->rrp = take((size_t)kW * cgx::multi_update_grid(ctx->n));
-    v->ms = reinterpret_cast<cgx::MultiScalars *>(take((sizeof(cgx::MultiScalars) + 7) / 8));
-    return off * sizeof(double);
+    Carver c{base};
+    v->B = c.take(vec);
+    v->X = c.take(vec);
+    v->R = c.take(vec);
+    v->P[0] = c.take(vec);
+    v->P[1] = c.take(vec);
+    v->Y = c.take(vec);
+    v->k1p = c.take((size_t)kW * k1p_stride(ctx->n));
+    v->rrp = c.take((size_t)kW * cgx::multi_update_grid(ctx->n));
+    v->ms = c.take_struct<cgx::MultiScalars>();
+    return c.bytes();
 }
 
 // The checks every multi entry point makes, in this order: context, problem, transport and storage, arguments.
 cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in, long ldin, const void *out, long ldout)
 {
-    if (!ctx) return CGX_ERR_BAD_ARG;
     const std::string fn(name);
-    if (!ctx->have_matrix) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no problem set");
-    if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": a cgx_solve_begin / cgx_solve_end pair is open");
-    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->nranks != 1 || ctx->shards.size() != 1)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": one GPU only (CGX_COMM_SELF)");
+    CGX_TRY(check_one_gpu_call(ctx, fn));
     if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
     if (nrhs < 1 || nrhs > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nrhs must be 1 .. CGX_MAX_RHS");
     if (!in || !out) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
@@ -68,24 +52,10 @@ cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in,
     return CGX_OK;
 }
 
-// The context's multi block, made (and zeroed: the pad rows of every vector stay 0) on first use.
+// The context's multi block, made on first use.
 cgx_status ensure_multi(cgx_ctx *ctx, MultiView *v)
 {
-    const size_t bytes = multi_layout(ctx, nullptr, v);
-    if (!ctx->multi) {
-        double *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, bytes));
-        const cgx_status st = [&]() -> cgx_status {
-            HIP_TRY(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
-            return CGX_OK;
-        }();
-        if (st != CGX_OK) {
-            (void)hipFree(p);
-            return st;
-        }
-        ctx->multi = p;
-        ctx->multi_bytes = bytes;
-    }
+    CGX_TRY(ensure_side_block(ctx, &ctx->multi, &ctx->multi_bytes, multi_layout(ctx, nullptr, v)));
     multi_layout(ctx, ctx->multi, v);
     return CGX_OK;
 }
@@ -119,25 +89,11 @@ cgx_status download(cgx_ctx *ctx, double *dst, long ld, const double *src, int n
     return CGX_OK;
 }
 
-// K1m fused of iteration k; every `profile_gemv`-th launch is event-timed, the first of the call never (as run_gemv_fused)
+// K1m fused of iteration k, event-timed where next_gemv_events says so (as run_gemv_fused, cgx_solve.cpp)
 cgx_status run_multi_fused(cgx_ctx *ctx, const MultiView &v, int nrhs, int k)
 {
-    const int every = ctx->cfg.profile_gemv;
-    const long long seq = ctx->gemv_seq++;
-    bool timed = false;
-    if (every > 0 && ctx->ev_used + 2 <= 4096) {
-        if (seq == 0) {
-            timed = ctx->cfg.profile_first != 0;
-            if (!timed) ctx->gemv_discarded++;
-        } else {
-            timed = ((seq - 1) % every) == 0;
-        }
-    }
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timed) {
-        CGX_TRY(take_event(ctx, &e0));
-        CGX_TRY(take_event(ctx, &e1));
-    }
+    hipEvent_t e0, e1;
+    CGX_TRY(next_gemv_events(ctx, &e0, &e1));
     cgx::MultiArgs g = plain_args(ctx, v, nrhs, v.P[k & 1]);
     g.p_new = v.P[(k + 1) & 1];
     g.r = v.R;
@@ -177,25 +133,13 @@ cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, do
 
     // the loop cg.cc:95-137: K1m + K3m per iteration; all_done is polled every check_every iterations, one batch kept queued
     const double t0 = wall_now();
-    const int every = std::max(1, ctx->cfg.check_every);
-    int k = 0, slot = 0;
-    bool pending[2] = {false, false}, stop = false;
-    while (k < ctx->max_iter && !stop) {
-        const int batch = std::min(ctx->max_iter - k, every);
-        for (int i = 0; i < batch; ++i, ++k) {
-            CGX_TRY(run_multi_fused(ctx, v, nrhs, k));
-            HIP_TRY(ctx, cgx::launch_multi_update(n, lda, nrhs, v.P[(k + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, k & 1, st));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags + 2 * slot, &v.ms->all_done, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipEventRecord(ctx->flag_ev[slot], st));
-        pending[slot] = true;
-        slot ^= 1;
-        if (pending[slot]) {
-            HIP_TRY(ctx, hipEventSynchronize(ctx->flag_ev[slot]));
-            pending[slot] = false;
-            if (ctx->h_flags[2 * slot]) stop = true;
-        }
-    }
+    auto iteration = [&](int i) -> cgx_status {
+        CGX_TRY(run_multi_fused(ctx, v, nrhs, i));
+        HIP_TRY(ctx, cgx::launch_multi_update(n, lda, nrhs, v.P[(i + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, i & 1, st));
+        return CGX_OK;
+    };
+    int k = 0;
+    CGX_TRY(run_polled(ctx, &v.ms->all_done, ctx->max_iter, false, iteration, &k));   // (no device-side window: steps_device_ms stays 0)
     // the head of iteration k for the columns still running (cg.cc:117-121,132), then x and the DEBUG norms (cg.cc:140-151)
     HIP_TRY(ctx, cgx::launch_multi_close(v.ms, v.rrp, n, nrhs, k, ctx->tol, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
@@ -213,19 +157,7 @@ cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, do
         memset(&base, 0, sizeof base);
         base.seconds_solve = wall_now() - t_begin;
         base.seconds_loop = t_loop;
-        base.gemv_launches = ctx->gemv_launches;
-        base.gemv_ms_avg = ctx->gemv_launches ? ctx->gemv_ms_sum / (double)ctx->gemv_launches : 0.0;
-        base.gemv_ms_min = ctx->gemv_ms_min;
-        base.gemv_ms_max = ctx->gemv_ms_max;
-        base.gemv_discarded = ctx->gemv_discarded;
-        if (!ctx->gemv_samples.empty()) {
-            std::vector<float> s(ctx->gemv_samples);
-            const size_t mid = s.size() / 2;
-            std::nth_element(s.begin(), s.begin() + mid, s.end());
-            double med = s[mid];
-            if (s.size() % 2 == 0) med = 0.5 * (med + *std::max_element(s.begin(), s.begin() + mid));
-            base.gemv_ms_median = med;
-        }
+        fill_k1_stats(ctx, &base);
         base.gemv_bytes = 8.0 * ((double)n * n + 2.0 * nrhs * n);
         for (int j = 0; j < nrhs; ++j) {
             cgx_result &o = res[j];

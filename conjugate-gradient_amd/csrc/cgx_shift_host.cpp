@@ -29,41 +29,20 @@ struct ShiftView {
 size_t shift_layout(const cgx_ctx *ctx, double *base, ShiftView *v)
 {
     const size_t vec = (size_t)kS * ctx->lda;
-    int g = 0;
-    for (int w = 1; w <= cgx::kMaxRhs; w *= 2) g = std::max(g, cgx::multi_gemv_grid(ctx->n, w));
-    size_t off = 0;
-    auto take = [&](size_t count) {
-        double *p = base ? base + off : nullptr;
-        off += (count + 15) / 16 * 16;   // 128-B aligned pieces
-        return p;
-    };
-    v->X = take(vec);
-    v->P = take(vec);
-    v->Y = take(vec);
-    v->k1p = take((size_t)kS * g);
-    v->ms = reinterpret_cast<cgx::MultiScalars *>(take((sizeof(cgx::MultiScalars) + 7) / 8));
-    v->ss = reinterpret_cast<cgx::ShiftScalars *>(take((sizeof(cgx::ShiftScalars) + 7) / 8));
-    return off * sizeof(double);
+    Carver c{base};
+    v->X = c.take(vec);
+    v->P = c.take(vec);
+    v->Y = c.take(vec);
+    v->k1p = c.take((size_t)kS * k1p_stride(ctx->n));
+    v->ms = c.take_struct<cgx::MultiScalars>();
+    v->ss = c.take_struct<cgx::ShiftScalars>();
+    return c.bytes();
 }
 
-// The context's shift block, made (and zeroed) on first use.
+// The context's shift block, made on first use.
 cgx_status ensure_shift(cgx_ctx *ctx, ShiftView *v)
 {
-    const size_t bytes = shift_layout(ctx, nullptr, v);
-    if (!ctx->shift) {
-        double *p = nullptr;
-        HIP_TRY(ctx, hipMalloc(&p, bytes));
-        const cgx_status st = [&]() -> cgx_status {
-            HIP_TRY(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
-            return CGX_OK;
-        }();
-        if (st != CGX_OK) {
-            (void)hipFree(p);
-            return st;
-        }
-        ctx->shift = p;
-        ctx->shift_bytes = bytes;
-    }
+    CGX_TRY(ensure_side_block(ctx, &ctx->shift, &ctx->shift_bytes, shift_layout(ctx, nullptr, v)));
     shift_layout(ctx, ctx->shift, v);
     return CGX_OK;
 }
@@ -71,12 +50,8 @@ cgx_status ensure_shift(cgx_ctx *ctx, ShiftView *v)
 // The checks in the order check_multi (cgx_multi_host.cpp) makes them: context, problem, transport and storage, arguments.
 cgx_status check_shifted(cgx_ctx *ctx, int nshift, const double *sigma, const double *X, long ldx)
 {
-    if (!ctx) return CGX_ERR_BAD_ARG;
     const std::string fn("cgx_solve_shifted");
-    if (!ctx->have_matrix) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no problem set");
-    if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": a cgx_solve_begin / cgx_solve_end pair is open");
-    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->nranks != 1 || ctx->shards.size() != 1)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": one GPU only (CGX_COMM_SELF)");
+    CGX_TRY(check_one_gpu_call(ctx, fn));
     if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense or CSR storage only (not CGX_MATRIX_BANDED)");
     if (ctx->precond != CGX_PRECOND_NONE)
         return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": no preconditioner (it breaks the collinearity of the shifted residuals; "
@@ -142,37 +117,14 @@ cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, doub
     // the loop cg.cc:95-137 as cgx_solve_steps runs it: the seed's done flag -- raised by the seed's own head or by the shift kernel
     // that found every shift frozen -- is polled every check_every iterations, one batch kept queued
     const double t0 = wall_now();
-    bool window_open = false;
-    if (ctx->cfg.profile_gemv && ctx->max_iter > 0) {
-        for (auto &e : ctx->steps_ev)
-            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[0], st));
-        window_open = true;
-    }
-    const int every = std::max(1, ctx->cfg.check_every);
-    int k = 0, slot = 0;
-    bool pending[2] = {false, false}, stop = false;
-    while (k < ctx->max_iter && !stop) {
-        const int batch = std::min(ctx->max_iter - k, every);
-        for (int i = 0; i < batch; ++i, ++k) {
-            CGX_TRY(enqueue_iteration(ctx, k));
-            a.k = k;
-            HIP_TRY(ctx, cgx::launch_shift_update(a, st));
-        }
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags + 2 * slot, &s.sc->done, 2 * sizeof(int), hipMemcpyDeviceToHost, st));
-        HIP_TRY(ctx, hipEventRecord(ctx->flag_ev[slot], st));
-        pending[slot] = true;
-        slot ^= 1;
-        if (pending[slot]) {
-            HIP_TRY(ctx, hipEventSynchronize(ctx->flag_ev[slot]));
-            pending[slot] = false;
-            if (ctx->h_flags[2 * slot]) stop = true;
-        }
-    }
-    if (window_open) {
-        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[1], st));
-        ctx->steps_ev_pending = true;
-    }
+    auto iteration = [&](int i) -> cgx_status {
+        CGX_TRY(enqueue_iteration(ctx, i));
+        a.k = i;
+        HIP_TRY(ctx, cgx::launch_shift_update(a, st));
+        return CGX_OK;
+    };
+    int k = 0;
+    CGX_TRY(run_polled(ctx, &s.sc->done, ctx->max_iter, ctx->cfg.profile_gemv && ctx->max_iter > 0, iteration, &k));
     HIP_TRY(ctx, cgx::launch_shift_close(v.ss, a.rrp, a.nrr, nshift, k, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
@@ -208,22 +160,8 @@ cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, doub
         memset(&base, 0, sizeof base);
         base.seconds_solve = wall_now() - t_begin;
         base.seconds_loop = t_loop;
-        base.gemv_launches = ctx->gemv_launches;
-        base.gemv_ms_avg = ctx->gemv_launches ? ctx->gemv_ms_sum / (double)ctx->gemv_launches : 0.0;
-        base.gemv_ms_min = ctx->gemv_ms_min;
-        base.gemv_ms_max = ctx->gemv_ms_max;
-        base.gemv_discarded = ctx->gemv_discarded;
-        base.steps_device_ms = ctx->steps_device_ms;
-        if (!ctx->gemv_samples.empty()) {
-            std::vector<float> sm(ctx->gemv_samples);
-            const size_t mid = sm.size() / 2;
-            std::nth_element(sm.begin(), sm.begin() + mid, sm.end());
-            double med = sm[mid];
-            if (sm.size() % 2 == 0) med = 0.5 * (med + *std::max_element(sm.begin(), sm.begin() + mid));
-            base.gemv_ms_median = med;
-        }
-        base.gemv_bytes = ctx->csr ? 12.0 * (double)s.csr.nnz + 8.0 * ((double)s.rows + 1) + 8.0 * s.rows + 8.0 * n
-                                   : 8.0 * ((double)s.rows * n + n + s.rows);
+        fill_k1_stats(ctx, &base);
+        base.gemv_bytes = one_gpu_gemv_bytes(ctx);
         for (int j = 0; j < nshift; ++j) {
             cgx_result &o = res[j];
             o = base;

@@ -17,7 +17,6 @@
 #include <sys/file.h>
 
 #include <cerrno>
-#include <climits>
 #include <thread>
 
 #include <algorithm>
@@ -103,131 +102,8 @@ cgx_status gather_segments(cgx_ctx *ctx, bool with_tail)
     }
 }
 
-}  // namespace cgxi
-
-namespace cgxi {
-
-// ---- block-Jacobi set-up -----------------------------------------------------
-// Behind prepare_jacobi's refusals and buffers, once per matrix and block size: W (block x lda doubles per shard, replicated like
-// dinv).  For t = 0 ... block-1 every shard writes column t of its own block rows into its Ap slice, the segment exchange gathers
-// the slices as it gathers the diagonal, and every shard unpacks them into W's row t (one rank: one launch writes all of W).
-// Then every shard inverts every block from its gathered copy, on the device, so all ranks take the same decision, after the
-// last exchange.
-static cgx_status prepare_block_jacobi(cgx_ctx *ctx)
-{
-    const int block = ctx->precond_block;
-    if (ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange)
-        return fail(ctx, CGX_ERR_UNSUPPORTED,
-                    "block Jacobi: the update kernel with the peer exchange inside has no block form (p2p_separate_exchange = 1 has)");
-    hipStream_t st = ctx->stream;
-    const size_t wbytes = (size_t)block * (size_t)ctx->lda * sizeof(double);
-    for (auto &s : ctx->shards) {
-        if (s.W && s.w_block != block) {
-            ctx->dinv_valid = false;
-            HIP_TRY(ctx, hipFree(s.W));
-            s.W = nullptr;
-            s.w_block = 0;
-        }
-        if (!s.W) {
-            ctx->dinv_valid = false;
-            const hipError_t e = fault_due(ctx) ? hipErrorUnknown : hipMalloc(&s.W, wbytes);
-            if (e != hipSuccess) {
-                s.W = nullptr;
-                quiesce(ctx);
-                char msg[200];
-                snprintf(msg, sizeof msg, "block Jacobi: %zu bytes of block inverses (8 x block %d x pitch %ld) could not be allocated: %s",
-                         wbytes, block, ctx->lda, hipGetErrorString(e));
-                return fail(ctx, e == hipErrorOutOfMemory ? CGX_ERR_OOM : CGX_ERR_HIP, msg);
-            }
-            s.w_block = block;
-        }
-    }
-    if (ctx->dinv_valid) return CGX_OK;
-    const bool one = ctx->shards.size() == 1 && ctx->nranks == 1;
-    auto slice = [&](Shard &s, int t0, int nt, double *dst, long stride) -> cgx_status {
-        if (ctx->csr) HIP_TRY(ctx, cgx::launch_csr_bj_col_slice(s.csr, ctx->n, s.rows, s.row0, block, t0, nt, dst, stride, st));
-        else HIP_TRY(ctx, cgx::launch_bj_col_slice(s.A, ctx->lda, ctx->n, s.rows, s.row0, block, t0, nt, dst, stride, st));
-        return CGX_OK;
-    };
-    if (one) {
-        Shard &s = ctx->shards[0];
-        HIP_TRY(ctx, hipMemsetAsync(s.W, 0, wbytes, st));   // the pad rows
-        CGX_TRY(slice(s, 0, block, s.W, ctx->lda));
-    } else {
-        for (int t = 0; t < block; ++t) {
-            for (auto &s : ctx->shards) CGX_TRY(slice(s, t, 1, s.Ap(), 0));
-            CGX_TRY(gather_segments(ctx, false));
-            for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_unpack_segments(s.apv, s.W + (size_t)t * ctx->lda, ctx->lda, st));
-        }
-    }
-    if (!ctx->d_jbad) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_jbad), sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_jbad, 0x7f, sizeof(int), st));   // 0x7f7f7f7f: above every row index
-    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_bj_invert(s.W, ctx->lda, ctx->n, block, ctx->d_jbad, st));
-    int bad = INT_MAX;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, ctx->d_jbad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (bad >= 0 && bad < ctx->n) {
-        char msg[200];
-        snprintf(msg, sizeof msg, "block Jacobi: the %d x %d diagonal block that begins at row %d is not positive definite "
-                                  "(a pivot of its factorisation is not finite and > 0)", block, block, bad);
-        return fail(ctx, CGX_ERR_BAD_ARG, msg);
-    }
-    ctx->dinv_valid = true;
-    return CGX_OK;
-}
-
-// ---- Jacobi set-up -----------------------------------------------------------
-// Collective, inside cgx_solve_begin: the refusals, the buffers, and -- once per matrix -- the diagonal.  Every shard reads the
-// diagonal of its own rows into its Ap slice, the transport's segment exchange gathers the slices, and every shard forms the
-// replicated dinv from its gathered copy.  The check (finite and > 0) runs on that copy, so all ranks take the same decision,
-// and only after the exchange, so no rank is left waiting in it.
-cgx_status prepare_jacobi(cgx_ctx *ctx)
-{
-    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, "Jacobi preconditioner: banded storage is not supported");
-    if (ctx->res_forced)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, "Jacobi preconditioner: the persistent kernels (gemv_variant 40000 / 50000) have no Jacobi form");
-    hipStream_t st = ctx->stream;
-    for (auto &s : ctx->shards) {
-        if (!s.dinv) {
-            const size_t zbytes = (size_t)(s.rv.S + (s.rv.S - s.rv.Sr)) * sizeof(double);
-            HIP_TRY(ctx, hipMalloc(&s.dinv, (size_t)ctx->lda * sizeof(double)));
-            HIP_TRY(ctx, hipMalloc(&s.zbuf, zbytes));
-            HIP_TRY(ctx, hipMemsetAsync(s.zbuf, 0, zbytes, st));
-        }
-        s.zv = s.rv;
-        s.zv.base = s.zbuf;
-    }
-    if (ctx->precond_block > 1) return prepare_block_jacobi(ctx);
-    if (ctx->dinv_valid) return CGX_OK;
-    for (auto &s : ctx->shards) {
-        if (ctx->csr)   // the entry with col == row, 0 where the row has none (then refused below like any entry <= 0)
-            HIP_TRY(ctx, cgx::launch_csr_diag_slice(s.csr, s.rows, s.row0, s.Ap(), st));
-        else
-            HIP_TRY(ctx, cgx::launch_diag_slice(s.A, ctx->lda, s.rows, s.row0, s.Ap(), st));
-    }
-    CGX_TRY(gather_segments(ctx, false));
-    if (!ctx->d_jbad) HIP_TRY(ctx, hipMalloc(reinterpret_cast<void **>(&ctx->d_jbad), sizeof(int)));
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_jbad, 0x7f, sizeof(int), st));   // 0x7f7f7f7f: above every row index
-    for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_jacobi_dinv(s.apv, ctx->n, ctx->lda, s.dinv, ctx->d_jbad, st));
-    int bad = INT_MAX;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, ctx->d_jbad, sizeof(int), hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (bad >= 0 && bad < ctx->n) {
-        const Shard &s = ctx->shards[0];
-        const int nl = s.apv.n_loc, P = s.apv.nranks;
-        const int q = nl > 0 ? std::min(bad / nl, P - 1) : P - 1;
-        double v = 0.0;
-        HIP_TRY(ctx, hipMemcpy(&v, s.apg + bad + (long)q * s.apv.seg_gap, sizeof(double), hipMemcpyDeviceToHost));
-        char msg[160];
-        snprintf(msg, sizeof msg, "Jacobi preconditioner: diagonal entry of row %d is %.17g (every entry must be finite and > 0)", bad, v);
-        return fail(ctx, CGX_ERR_BAD_ARG, msg);
-    }
-    ctx->dinv_valid = true;
-    return CGX_OK;
-}
-
 // ---- K1 with optional event bracketing -----------------------------------------------------------
-cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)
+static cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)   // an event of the K1 timing pool
 {
     if (ctx->ev_used == ctx->ev_pool.size()) {
         hipEvent_t e;
@@ -238,13 +114,39 @@ cgx_status take_event(cgx_ctx *ctx, hipEvent_t *out)
     return CGX_OK;
 }
 
-}  // namespace cgxi
-
-namespace {
+// Every `profile_gemv`-th K1 launch of a steps call is bracketed with HIP events; this decides whether the next one is.
+// The first launch of a steps call starts on a drained stream, right after a host-side synchronisation: whatever the
+// runtime or the clocks do at that point lands on it (the round-1 driver run recorded 2.06 ms there against 1.21 for
+// every other launch).  It is counted as discarded, never as a sample (cfg.profile_first overrides, for diagnostics).
+// Every later launch has the previous iteration's K3 queued in front of it.
+// At most 2048 timed launches per cgx_solve_steps call: the event pool stays bounded however long the run is.
+// gemv_timed_last is for take_update_events below; cgx_solve_multi sets it through here as well and never reads it (its update
+// kernel is not event-timed: nothing on that path calls take_update_events).
+cgx_status next_gemv_events(cgx_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1)
+{
+    *e0 = *e1 = nullptr;
+    const int every = ctx->cfg.profile_gemv;
+    const long long seq = ctx->gemv_seq++;
+    bool timed = false;
+    if (every > 0 && ctx->ev_used + 2 <= 4096) {
+        if (seq == 0) {
+            timed = ctx->cfg.profile_first != 0;
+            if (!timed) ctx->gemv_discarded++;
+        } else {
+            timed = ((seq - 1) % every) == 0;
+        }
+    }
+    ctx->gemv_timed_last = timed;
+    if (timed) {
+        CGX_TRY(take_event(ctx, e0));
+        CGX_TRY(take_event(ctx, e1));
+    }
+    return CGX_OK;
+}
 
 // cfg.profile_update: an event pair for the update kernel of an iteration whose K1 was timed (first shard only: one
 // sample per iteration), or two null handles.
-cgx_status take_update_events(cgx_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1)
+static cgx_status take_update_events(cgx_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1)
 {
     *e0 = *e1 = nullptr;
     if (!ctx->cfg.profile_update || !ctx->gemv_timed_last || ctx->cfg.profile_markers) return CGX_OK;
@@ -257,10 +159,6 @@ cgx_status take_update_events(cgx_ctx *ctx, hipEvent_t *e0, hipEvent_t *e1)
     *e1 = ctx->upd_pool[ctx->upd_used++];
     return CGX_OK;
 }
-
-}  // namespace
-
-namespace cgxi {
 
 // K1, plain form (vector given): initial residual, DEBUG verification, probes.
 cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full)
@@ -278,36 +176,16 @@ cgx_status run_gemv_plain(cgx_ctx *ctx, Shard &s, const double *v_full)
     return CGX_OK;
 }
 
-// K1, fused form of iteration k; every `profile_gemv`-th launch is bracketed with HIP events.
-cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
+// K1, fused form of iteration k, event-timed where next_gemv_events says so.
+static cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
 {
-    const int every = ctx->cfg.profile_gemv;
-    // The first launch of a steps call starts on a drained stream, right after a host-side synchronisation: whatever the
-    // runtime or the clocks do at that point lands on it (the round-1 driver run recorded 2.06 ms there against 1.21 for
-    // every other launch).  It is counted as discarded, never as a sample (cfg.profile_first overrides, for diagnostics).
-    // Every later launch has the previous iteration's K3 queued in front of it.
-    // At most 2048 timed launches per cgx_solve_steps call: the event pool stays bounded however long the run is.
-    const long long seq = ctx->gemv_seq++;
-    bool timed = false;
-    if (every > 0 && ctx->ev_used + 2 <= 4096) {
-        if (seq == 0) {
-            timed = ctx->cfg.profile_first != 0;
-            if (!timed) ctx->gemv_discarded++;
-        } else {
-            timed = ((seq - 1) % every) == 0;
-        }
+    hipEvent_t e0, e1, m1 = nullptr;
+    CGX_TRY(next_gemv_events(ctx, &e0, &e1));
+    if (e0 && ctx->cfg.profile_markers) {   // old form: marker packets around the dispatch (kept for A/B, tools/window_probe.py)
+        HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
+        m1 = e1;
+        e0 = e1 = nullptr;
     }
-    ctx->gemv_timed_last = timed;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (timed) {
-        CGX_TRY(take_event(ctx, &e0));
-        CGX_TRY(take_event(ctx, &e1));
-        if (ctx->cfg.profile_markers) {   // old form: marker packets around the dispatch (kept for A/B, tools/window_probe.py)
-            HIP_TRY(ctx, hipEventRecord(e0, ctx->stream));
-            e0 = e1 = nullptr;
-        }
-    }
-    hipEvent_t m1 = (timed && ctx->cfg.profile_markers) ? ctx->ev_pool[ctx->ev_used - 1] : nullptr;
     const bool pc = ctx->precond == CGX_PRECOND_JACOBI;   // p = z + beta p_old: K1 reads z where it reads r otherwise
     if (ctx->csr)
         HIP_TRY(ctx, cgx::launch_spmv_csr_fused(s.plan, s.csr, s.rows, s.row0, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1], pc ? s.zv : s.rv,
@@ -410,31 +288,34 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
     return CGX_OK;
 }
 
+// What a raised error word of the direct peer exchange means.
+static cgx_status p2p_err_status(cgx_ctx *ctx, int word)
+{
+    if (word) return fail(ctx, CGX_ERR_P2P, "direct peer exchange: a wait for a peer's flag expired (peer dead or IPC not coherent)");
+    return CGX_OK;
+}
+
 // After a stream sync: did any bounded wait of the direct peer exchange expire?
 cgx_status check_p2p_error(cgx_ctx *ctx)
 {
     if (ctx->cfg.comm_mode != CGX_COMM_P2P || !ctx->d_p2p_err) return CGX_OK;
     int e = 0;
     HIP_TRY(ctx, hipMemcpy(&e, ctx->d_p2p_err, sizeof(int), hipMemcpyDeviceToHost));
-    if (e) return fail(ctx, CGX_ERR_P2P, "direct peer exchange: a wait for a peer's flag expired (peer dead or IPC not coherent)");
-    return CGX_OK;
+    return p2p_err_status(ctx, e);
 }
 
 // {done, k_final} and the P2P error word in ONE pass: two small copies into pinned memory, one stream sync.
-cgx_status read_flags_sync(cgx_ctx *ctx)
+static cgx_status read_flags_sync(cgx_ctx *ctx)
 {
     Shard &s = ctx->shards[0];
     int *flags = ctx->h_flags + 4;   // third pinned slot {done, k_final, p2p error}: a pageable destination would be staged by the runtime
-    const bool p2p = ctx->cfg.comm_mode == CGX_COMM_P2P && ctx->d_p2p_err;
-    flags[2] = 0;
+    flags[2] = 0;   // (stays 0 where there is no error word to copy)
     HIP_TRY(ctx, hipMemcpyAsync(flags, &s.sc->done, 2 * sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
-    if (p2p) HIP_TRY(ctx, hipMemcpyAsync(flags + 2, ctx->d_p2p_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->cfg.comm_mode == CGX_COMM_P2P && ctx->d_p2p_err) HIP_TRY(ctx, hipMemcpyAsync(flags + 2, ctx->d_p2p_err, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->done = flags[0] != 0;
     ctx->k_final = flags[1];
-    if (p2p && flags[2])
-        return fail(ctx, CGX_ERR_P2P, "direct peer exchange: a wait for a peer's flag expired (peer dead or IPC not coherent)");
-    return CGX_OK;
+    return p2p_err_status(ctx, flags[2]);
 }
 
 // The loop cg.cc:95-137 as launches of a persistent kernel (cgx_resident.hip: A on the chip; cgx_stream.hip: A streamed): up
@@ -629,6 +510,94 @@ cgx_status resident_steps(cgx_ctx *ctx, int nsteps, int *redo)
     return CGX_OK;
 }
 
+// ---- shared by cgx_solve_end, cgx_solve_multi and cgx_solve_shifted ------------------------------------
+// The K1 statistics of the most recent steps call (harvested) into a result.
+void fill_k1_stats(const cgx_ctx *ctx, cgx_result *res)
+{
+    res->gemv_launches = ctx->gemv_launches;
+    res->gemv_ms_avg = ctx->gemv_launches ? ctx->gemv_ms_sum / (double)ctx->gemv_launches : 0.0;
+    res->gemv_ms_min = ctx->gemv_ms_min;
+    res->gemv_ms_max = ctx->gemv_ms_max;
+    res->gemv_discarded = ctx->gemv_discarded;
+    res->steps_device_ms = ctx->steps_device_ms;
+    if (!ctx->gemv_samples.empty()) {
+        std::vector<float> v(ctx->gemv_samples);
+        const size_t mid = v.size() / 2;
+        std::nth_element(v.begin(), v.begin() + mid, v.end());
+        double med = v[mid];
+        if (v.size() % 2 == 0) med = 0.5 * (med + *std::max_element(v.begin(), v.begin() + mid));
+        res->gemv_ms_median = med;
+    }
+}
+
+// CSR: values, columns, row pointers, Ap written and p read once (the dense definition's counterpart)
+double one_gpu_gemv_bytes(const cgx_ctx *ctx)
+{
+    const Shard &s = ctx->shards[0];
+    return ctx->csr      ? 12.0 * (double)s.csr.nnz + 8.0 * ((double)s.rows + 1) + 8.0 * s.rows + 8.0 * ctx->n
+           : ctx->banded ? 8.0 * ((double)s.rows * s.dia.ndiag + 2.0 * s.rows)
+                         : 8.0 * ((double)s.rows * ctx->n + ctx->n + s.rows);
+}
+
+cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (!ctx->have_matrix) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no problem set");
+    if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": a cgx_solve_begin / cgx_solve_end pair is open");
+    if (ctx->cfg.comm_mode != CGX_COMM_SELF || ctx->nranks != 1 || ctx->shards.size() != 1)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": one GPU only (CGX_COMM_SELF)");
+    return CGX_OK;
+}
+
+// (zeroed: the pad rows of every vector in the block stay 0)
+cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes)
+{
+    if (*block) return CGX_OK;
+    double *p = nullptr;
+    HIP_TRY(ctx, hipMalloc(&p, bytes));
+    const cgx_status st = [&]() -> cgx_status {
+        HIP_TRY(ctx, hipMemsetAsync(p, 0, bytes, ctx->stream));
+        return CGX_OK;
+    }();
+    if (st != CGX_OK) {
+        (void)hipFree(p);
+        return st;
+    }
+    *block = p;
+    *block_bytes = bytes;
+    return CGX_OK;
+}
+
+// What cgx_solve_end reports apart from the K1 timing.  rr: r.r of the last two iterations by parity; sums: |A x - b|^2, |b|^2, |x|^2
+static void fill_solve_result(const cgx_ctx *ctx, cgx_result *res, int k_exit, const double *rr, const double *sums)
+{
+    memset(res, 0, sizeof *res);
+    res->iterations = k_exit;
+    res->converged = ctx->done ? 1 : 0;
+    res->residual_prev = std::sqrt(rr[k_exit & 1]);             // sqrt(rsold) as printed, cg.cc:152-153
+    res->residual_last = std::sqrt(rr[(k_exit + 1) & 1]);
+    if (!ctx->done) res->residual_last = res->residual_prev;    // loop ran out: rsold == rsnew (cg.cc:132)
+    res->x_norm = std::sqrt(sums[2]);
+    res->rel_residual = std::sqrt(sums[0]) / std::sqrt(sums[1]);
+    res->seconds_solve = wall_now() - ctx->t_begin;
+    res->seconds_loop = ctx->t_loop;
+    res->gemv_bytes = one_gpu_gemv_bytes(ctx);
+}
+
+// One body behind cgx_get_gemv_samples and cgx_get_update_samples.
+static cgx_status copy_samples(cgx_ctx *ctx, std::vector<float> cgx_ctx::*which, double *ms_out, int cap, int *count)
+{
+    if (!ctx || !count || (cap > 0 && !ms_out)) return CGX_ERR_BAD_ARG;
+    if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) {
+        if (hipSetDevice(ctx->device) != hipSuccess) return CGX_ERR_HIP;
+        CGX_TRY(harvest_gemv_events(ctx));
+    }
+    const std::vector<float> &v = ctx->*which;
+    *count = (int)v.size();
+    for (int i = 0; i < cap && i < *count; ++i) ms_out[i] = v[(size_t)i];
+    return CGX_OK;
+}
+
 }  // namespace cgxi
 
 extern "C" {
@@ -716,39 +685,15 @@ cgx_status cgx_solve_steps(cgx_ctx *ctx, int nsteps, int *done_out)
         }
         nsteps = redo;   // a persistent launch's waits expired: the rest of the call runs below, on the per-launch path
     }
-    bool window_open = false;   // the start marker of THIS call is on the stream (a stop marker is only paired with that)
-    if (ctx->cfg.profile_gemv && nsteps > 0 && !ctx->done) {
-        for (auto &e : ctx->steps_ev)
-            if (!e) HIP_TRY(ctx, hipEventCreate(&e));
-        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[0], ctx->stream));
-        window_open = true;
-    }
-    const int every = ctx->cfg.check_every;
-    int slot = 0;
-    bool pending[2] = {false, false};
-    bool stop = ctx->done;
-    int left = std::min(nsteps, ctx->max_iter - ctx->k);
-    while (left > 0 && !stop) {
-        const int batch = std::min(left, every);
-        for (int i = 0; i < batch; ++i) CGX_TRY(enqueue_iteration(ctx, ctx->k + i));
-        ctx->k += batch;
-        left -= batch;
-        // publish {done,k_final} after this batch; look at the batch BEFORE it, so one batch stays queued
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->h_flags + 2 * slot, &ctx->shards[0].sc->done, 2 * sizeof(int),
-                                    hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(ctx, hipEventRecord(ctx->flag_ev[slot], ctx->stream));
-        pending[slot] = true;
-        slot ^= 1;
-        if (pending[slot]) {
-            HIP_TRY(ctx, hipEventSynchronize(ctx->flag_ev[slot]));
-            pending[slot] = false;
-            if (ctx->h_flags[2 * slot]) stop = true;   // identical on every rank: rsnew is bit-identical (cg.cc:117-121)
-        }
-    }
-    if (window_open) {
-        HIP_TRY(ctx, hipEventRecord(ctx->steps_ev[1], ctx->stream));
-        ctx->steps_ev_pending = true;
-    }
+    // the loop cg.cc:95-137: {done, k_final} is polled every check_every iterations, one batch kept queued (run_polled)
+    const int k0 = ctx->k;
+    const int count = ctx->done ? 0 : std::min(nsteps, ctx->max_iter - k0);
+    const bool window = ctx->cfg.profile_gemv && nsteps > 0 && !ctx->done;
+    int ran = 0;
+    const cgx_status looped = run_polled(ctx, &ctx->shards[0].sc->done, count, window,
+                                         [&](int i) { return enqueue_iteration(ctx, k0 + i); }, &ran);
+    ctx->k = k0 + ran;   // (also where a batch failed: the batches before it are on the stream)
+    CGX_TRY(looped);
     CGX_TRY(read_flags_sync(ctx));
     // the event pairs are read later (cgx_get_gemv_samples / cgx_solve_end): the elapsed-time queries of a few dozen
     // pairs are not part of the loop and must not sit inside a caller's timing window
@@ -787,19 +732,7 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
         if (x) memcpy(x, ctx->h_stage, (size_t)ctx->n * sizeof(double));
         ctx->in_solve = false;
         ctx->lean = false;
-        if (res) {
-            memset(res, 0, sizeof *res);
-            res->iterations = k_exit;
-            res->converged = ctx->done ? 1 : 0;
-            res->residual_prev = std::sqrt(o[3 + (k_exit & 1)]);           // sqrt(rsold) as printed, cg.cc:152-153
-            res->residual_last = std::sqrt(o[3 + ((k_exit + 1) & 1)]);
-            if (!ctx->done) res->residual_last = res->residual_prev;        // loop ran out: rsold == rsnew (cg.cc:132)
-            res->x_norm = std::sqrt(o[2]);
-            res->rel_residual = std::sqrt(o[0]) / std::sqrt(o[1]);
-            res->seconds_solve = wall_now() - ctx->t_begin;
-            res->seconds_loop = ctx->t_loop;
-            res->gemv_bytes = 8.0 * ((double)s.rows * ctx->n + ctx->n + s.rows);
-        }
+        if (res) fill_solve_result(ctx, res, k_exit, o + 3, o);   // (the K1 timing fields stay 0: the persistent path times no launch)
         return CGX_OK;
     }
     ctx->lean = false;
@@ -838,61 +771,20 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
 
     ctx->in_solve = false;
     if (res) {
-        memset(res, 0, sizeof *res);
-        res->iterations = k_exit;
-        res->converged = ctx->done ? 1 : 0;
-        const double *rr = pc ? hs.rr : hs.rs;                       // Jacobi: rs[] holds r.z, rr[] r.r
-        res->residual_prev = std::sqrt(rr[k_exit & 1]);             // sqrt(rsold) as printed, cg.cc:152-153
-        res->residual_last = std::sqrt(rr[(k_exit + 1) & 1]);
-        if (!ctx->done) res->residual_last = res->residual_prev;    // loop ran out: rsold == rsnew (cg.cc:132)
-        res->x_norm = std::sqrt(sums[2]);
-        res->rel_residual = std::sqrt(sums[0]) / std::sqrt(sums[1]);
-        res->seconds_solve = wall_now() - ctx->t_begin;
-        res->seconds_loop = ctx->t_loop;
-        res->gemv_launches = ctx->gemv_launches;
-        res->gemv_ms_avg = ctx->gemv_launches ? ctx->gemv_ms_sum / (double)ctx->gemv_launches : 0.0;
-        res->gemv_ms_min = ctx->gemv_ms_min;
-        res->gemv_ms_max = ctx->gemv_ms_max;
-        res->gemv_discarded = ctx->gemv_discarded;
-        res->steps_device_ms = ctx->steps_device_ms;
-        if (!ctx->gemv_samples.empty()) {
-            std::vector<float> v(ctx->gemv_samples);
-            const size_t mid = v.size() / 2;
-            std::nth_element(v.begin(), v.begin() + mid, v.end());
-            double med = v[mid];
-            if (v.size() % 2 == 0) med = 0.5 * (med + *std::max_element(v.begin(), v.begin() + mid));
-            res->gemv_ms_median = med;
-        }
-        // CSR: values, columns, row pointers, Ap written and p read once (the dense definition's counterpart)
-        res->gemv_bytes = ctx->csr      ? 12.0 * (double)s0.csr.nnz + 8.0 * ((double)s0.rows + 1) + 8.0 * s0.rows + 8.0 * ctx->n
-                          : ctx->banded ? 8.0 * ((double)s0.rows * s0.dia.ndiag + 2.0 * s0.rows)
-                                        : 8.0 * ((double)s0.rows * ctx->n + ctx->n + s0.rows);
+        fill_solve_result(ctx, res, k_exit, pc ? hs.rr : hs.rs, sums);   // Jacobi: rs[] holds r.z, rr[] r.r
+        fill_k1_stats(ctx, res);
     }
     return CGX_OK;
 }
 
 cgx_status cgx_get_gemv_samples(cgx_ctx *ctx, double *ms_out, int cap, int *count)
 {
-    if (!ctx || !count || (cap > 0 && !ms_out)) return CGX_ERR_BAD_ARG;
-    if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) {
-        if (hipSetDevice(ctx->device) != hipSuccess) return CGX_ERR_HIP;
-        CGX_TRY(harvest_gemv_events(ctx));
-    }
-    *count = (int)ctx->gemv_samples.size();
-    for (int i = 0; i < cap && i < *count; ++i) ms_out[i] = ctx->gemv_samples[(size_t)i];
-    return CGX_OK;
+    return copy_samples(ctx, &cgx_ctx::gemv_samples, ms_out, cap, count);
 }
 
 cgx_status cgx_get_update_samples(cgx_ctx *ctx, double *ms_out, int cap, int *count)
 {
-    if (!ctx || !count || (cap > 0 && !ms_out)) return CGX_ERR_BAD_ARG;
-    if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) {
-        if (hipSetDevice(ctx->device) != hipSuccess) return CGX_ERR_HIP;
-        CGX_TRY(harvest_gemv_events(ctx));
-    }
-    *count = (int)ctx->upd_samples.size();
-    for (int i = 0; i < cap && i < *count; ++i) ms_out[i] = ctx->upd_samples[(size_t)i];
-    return CGX_OK;
+    return copy_samples(ctx, &cgx_ctx::upd_samples, ms_out, cap, count);
 }
 
 cgx_status cgx_solve(cgx_ctx *ctx, double *x, cgx_result *res)

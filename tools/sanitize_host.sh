@@ -10,7 +10,8 @@ P=$R/conjugate-gradient_amd
 CL=/opt/rocm/lib/llvm/bin/clang++
 W=$(mktemp -d /tmp/cgx_san.XXXX)
 cd $W
-make -C $P -s build/cgx_kernels.o
+DEV="cgx_kernels cgx_csr cgx_p2p cgx_symv cgx_multi cgx_shift cgx_resident cgx_stream"   # the launchers the host objects call
+make -C $P -s $(for f in $DEV; do echo build/$f.o; done)
 python3 - <<'PY'
 page = 4096
 head = "%%MatrixMarket matrix coordinate real general\n"
@@ -30,10 +31,10 @@ FILES="$R/tests/golden/lap2D_5pt_n100.mtx page.mtx short.mtx bad.mtx longtok.mtx
 fail=0
 for san in "address,undefined" "thread"; do
   d=obj_${san%%,*}; mkdir -p $d
-  for f in cgx_matrix cgx_context cgx_solve cgx_probe cgx_rccl; do
+  for f in cgx_matrix cgx_context cgx_solve cgx_precond cgx_probe cgx_rccl; do
     $CL -x c++ -D__HIP_PLATFORM_AMD__ -fsanitize=$san -fno-omit-frame-pointer -g -O1 -std=c++17 -fPIC -w -I/opt/rocm/include -I$R/include -c $P/csrc/$f.cpp -o $d/$f.o
   done
-  $CL -fsanitize=$san -g -O1 -std=c++17 -I$R/include $R/tools/sanitize/parser_harness.cc $d/*.o $P/build/cgx_kernels.o -o harness_${san%%,*} \
+  $CL -fsanitize=$san -g -O1 -std=c++17 -I$R/include $R/tools/sanitize/parser_harness.cc $d/*.o $(for f in $DEV; do echo $P/build/$f.o; done) -o harness_${san%%,*} \
       -L/opt/rocm/lib -lamdhip64 -ldl -lpthread -Wl,-rpath,/opt/rocm/lib
   ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1 TSAN_OPTIONS=report_signal_unsafe=0 ./harness_${san%%,*} $FILES > out_${san%%,*}.txt 2>&1 || true
   if grep -E "ERROR: AddressSanitizer|runtime error:|WARNING: ThreadSanitizer" out_${san%%,*}.txt; then fail=1; fi
