@@ -2,6 +2,7 @@
 16 shifts from one Krylov sequence.
 
 - every shift against oracle.solve of the shifted dense matrix (fixed iterations and converged), dense, symmetric K1 and CSR;
+- what every shift reports (both residuals, x_norm, rel_residual) against the oracle and a host recomputation, dense and CSR;
 - sigma = 0 against cgx_solve on the same context, bit for bit;
 - independence of the other shifts, their number, their order and check_every;
 - the underflow guard of zeta, the early end when every shift is frozen;
@@ -87,6 +88,34 @@ def test_fixed_iterations_against_oracle(gpu_pkg, oracle, kind, n, storage, vari
         print("fixed %s n=%d %s sigma=%g: iterations %d, |dx|/|x| = %.2e" % (kind, n, storage, sigma, res[j]["iterations"], err))
         assert res[j]["iterations"] == ro["iterations"] == iters, (sigma, res[j], ro)
         assert err <= 1e-12, (sigma, err)
+
+
+@pytest.mark.parametrize("storage", ["dense", "csr"])
+def test_reported_numbers_against_oracle(gpu_pkg, oracle, storage):
+    """What a shift reports, against values computed outside the library (for sigma != 0 they come from k_shift_norms and the
+    |zeta| sqrt(r.r) stores alone): residual_prev and residual_last against the oracle's on the shifted matrix, 1e-9 relative
+    (the bar of tests/test_gpu_parity.py test_full_size_properties for reported residuals); x_norm against ||x||, 1e-12;
+    rel_residual against ||(A + sigma I) x - b|| / ||b|| recomputed on the host from the returned x, 1e-9 relative plus the
+    rounding allowance of tests/test_gpu_jacobi_scaled.py _check_rel_residual at 6 entries per row."""
+    from test_gpu_jacobi_scaled import _check_rel_residual
+    n, iters = 1000, 12
+    A, b = _problem(oracle, "lap2d", n)
+    with _solver(gpu_pkg, "lap2d", n, storage) as s:
+        assert (s.gemv_plan()["variant"] == 7) == (storage == "csr"), s.gemv_plan()
+        s.set_max_iter(iters)
+        s.tolerance(0.0)
+        X, res = s.solve_shifted(S7)
+    for j, sigma in enumerate(S7):
+        _, ro = _reference(oracle, "lap2d", n, sigma, iters, 0.0)
+        xn = float(np.linalg.norm(X[j]))
+        offs = {k: abs(res[j][k] - ro[k]) / ro[k] for k in ("residual_prev", "residual_last")}
+        print("reported %s sigma=%g: residual_prev off by %.2e, residual_last by %.2e, x_norm by %.2e" % (
+            storage, sigma, offs["residual_prev"], offs["residual_last"], abs(res[j]["x_norm"] - xn) / xn))
+        assert res[j]["iterations"] == ro["iterations"] == iters, (sigma, res[j], ro)
+        for k, off in offs.items():
+            assert off <= 1e-9, (sigma, k, res[j][k], ro[k])
+        assert abs(res[j]["x_norm"] - xn) <= 1e-12 * xn, (sigma, res[j]["x_norm"], xn)
+        _check_rel_residual(res[j], A @ X[j] + sigma * X[j], np.abs(A) @ np.abs(X[j]) + sigma * np.abs(X[j]), b, 6, (storage, sigma))
 
 
 # ---- 2. converged ---------------------------------------------------------------------------------------------------------------------
