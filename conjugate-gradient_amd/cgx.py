@@ -37,11 +37,15 @@ EXPORTS = [
     "cgx_set_preconditioner", "cgx_get_preconditioner",
     "cgx_set_preconditioner_block", "cgx_get_preconditioner_block", "cgx_probe_get_precond_blocks",
     "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
+    "cgx_set_preconditioner_rank", "cgx_get_preconditioner_rank", "cgx_set_preconditioner_shift", "cgx_get_preconditioner_shift",
+    "cgx_probe_get_precond_lowrank", "cgx_probe_precond_apply",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
-_PRECOND_NAMES = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI}
+PRECOND_PIVCHOL = 2                   # the pivoted-Cholesky low-rank factor: one GPU, dense storage
+MAX_PRECOND_RANK = 256                # CGX_MAX_PRECOND_RANK: cgx_set_preconditioner_rank
+_PRECOND_NAMES = {None: PRECOND_NONE, "jacobi": PRECOND_JACOBI, "pivchol": PRECOND_PIVCHOL}
 PRECOND_BLOCKS = (1, 2, 4, 8, 16, 32, 64, 128, 256)   # cgx_set_preconditioner_block
 
 
@@ -159,6 +163,12 @@ def lib():
         L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner_block.argtypes = [vp, ip]
         L.cgx_probe_get_precond_blocks.argtypes = [vp, C.c_int, dp]
+        L.cgx_set_preconditioner_rank.argtypes = [vp, C.c_int]
+        L.cgx_get_preconditioner_rank.argtypes = [vp, ip]
+        L.cgx_set_preconditioner_shift.argtypes = [vp, C.c_double]
+        L.cgx_get_preconditioner_shift.argtypes = [vp, dp, dp]
+        L.cgx_probe_get_precond_lowrank.argtypes = [vp, ip, dp, dp]
+        L.cgx_probe_precond_apply.argtypes = [vp, dp, dp]
         L.cgx_probe_gemv_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, dp]
         L.cgx_probe_parse_matrix_market.argtypes = [C.c_char_p, C.c_int, ip, ip, ip, ip, ip, ip, dp, C.c_long, C.c_char_p, C.c_int]
         for name in EXPORTS:
@@ -366,20 +376,58 @@ class CGSolver:
     def tolerance(self, tol):
         self._check(lib().cgx_set_tolerance(self._h, float(tol)))
 
-    def set_preconditioner(self, kind, block=1):
-        """None (plain CG) or "jacobi": takes effect at the next solve (include/cgx.h cgx_set_preconditioner).  block > 1 makes
-        "jacobi" block Jacobi with the block x block diagonal blocks (cgx_set_preconditioner_block; 1 = point Jacobi)."""
+    def set_preconditioner(self, kind, block=1, rank=32, shift=0.0):
+        """None (plain CG), "jacobi" or "pivchol": takes effect at the next solve (include/cgx.h cgx_set_preconditioner).  block > 1
+        makes "jacobi" block Jacobi with the block x block diagonal blocks (cgx_set_preconditioner_block; 1 = point Jacobi).
+        rank (1 ... MAX_PRECOND_RANK) and shift (0 = automatic, else positive and finite) belong to "pivchol", the rank-k pivoted
+        Cholesky factor plus shift of a dense SPD matrix on one GPU (cgx_set_preconditioner_rank / _shift)."""
         if kind not in _PRECOND_NAMES:
-            raise ValueError("preconditioner must be None or 'jacobi', not %r" % (kind,))
+            raise ValueError("preconditioner must be None, 'jacobi' or 'pivchol', not %r" % (kind,))
         if isinstance(block, bool) or not isinstance(block, (int, np.integer)) or int(block) not in PRECOND_BLOCKS:
             raise ValueError("block must be one of %r, not %r" % (PRECOND_BLOCKS, block))
+        if isinstance(rank, bool) or not isinstance(rank, (int, np.integer)) or not 1 <= int(rank) <= MAX_PRECOND_RANK:
+            raise ValueError("rank must be an integer 1 ... %d, not %r" % (MAX_PRECOND_RANK, rank))
+        if isinstance(shift, bool) or not isinstance(shift, (int, float, np.integer, np.floating)) or not 0.0 <= float(shift) < float("inf"):
+            raise ValueError("shift must be 0 (automatic) or positive and finite, not %r" % (shift,))
         self._check(lib().cgx_set_preconditioner(self._h, _PRECOND_NAMES[kind]))
         self._check(lib().cgx_set_preconditioner_block(self._h, int(block)))
+        if kind == "pivchol":   # (another kind leaves the rank, the shift and the factor made with them as they are)
+            self._check(lib().cgx_set_preconditioner_rank(self._h, int(rank)))
+            self._check(lib().cgx_set_preconditioner_shift(self._h, float(shift)))
 
     def preconditioner_block(self):
         b = C.c_int()
         self._check(lib().cgx_get_preconditioner_block(self._h, C.byref(b)))
         return b.value
+
+    def preconditioner_rank(self):
+        k = C.c_int()
+        self._check(lib().cgx_get_preconditioner_rank(self._h, C.byref(k)))
+        return k.value
+
+    def preconditioner_shift(self):
+        """(the shift as set, the shift of the factor in use: 0.0 until a solve has made one)."""
+        a, b = C.c_double(), C.c_double()
+        self._check(lib().cgx_get_preconditioner_shift(self._h, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+    def _probe_precond_lowrank(self):
+        """Test hook: (pivots, L as an (n, rank) array, the shift in use) of the "pivchol" factor."""
+        k = self.preconditioner_rank()
+        piv = np.zeros(k, dtype=np.int32)
+        L = np.zeros((self.n(), k), dtype=np.float64)
+        d = C.c_double()
+        self._check(lib().cgx_probe_get_precond_lowrank(self._h, piv.ctypes.data_as(C.POINTER(C.c_int)), _dp(L), C.byref(d)))
+        return piv, L, d.value
+
+    def _probe_precond_apply(self, r):
+        """Test hook: z = P^-1 r through the loop's kernels."""
+        r = np.ascontiguousarray(r, dtype=np.float64)
+        if r.shape != (self.n(),):
+            raise ValueError("r must have n entries")
+        z = np.zeros_like(r)
+        self._check(lib().cgx_probe_precond_apply(self._h, _dp(r), _dp(z)))
+        return z
 
     def _probe_precond_blocks(self, local_shard=0):
         """Test hook: the block inverses of a local shard as an (n, block) array, row i = (D_b^-1)(i, s(i) : s(i) + block)."""

@@ -122,6 +122,13 @@ void free_problem(cgx_ctx *ctx)
     ctx->dinv_valid = false;
     (void)hipFree(ctx->d_jbad);
     ctx->d_jbad = nullptr;
+    ctx->lr_valid = false;
+    (void)hipFree(ctx->lr_L);
+    ctx->lr_L = nullptr;
+    ctx->lr_L_rank = 0;
+    (void)hipFree(ctx->lr_block);
+    ctx->lr_block = nullptr;
+    ctx->lr_block_bytes = 0;
 }
 
 // Mailbox bytes before the segment channel: flag words, chunk flag words, channel 0 (16-B slots) and channel 2 (kSlots doubles).
@@ -461,6 +468,7 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
 cgx_status plan_symmetric(cgx_ctx *ctx)
 {
     ctx->dinv_valid = false;   // behind every writer of A: the next preconditioned solve extracts the diagonal again
+    ctx->lr_valid = false;     // ... or factors A again
     if (ctx->shards.size() != 1 || ctx->nranks != 1 || ctx->sparse() || ctx->chunked) return CGX_OK;
     Shard &s = ctx->shards[0];
     int variant = ctx->cfg.gemv_variant;
@@ -940,7 +948,7 @@ cgx_status cgx_set_max_iter(cgx_ctx *ctx, int max_iter)
 cgx_status cgx_set_preconditioner(cgx_ctx *ctx, int kind)
 {
     if (!ctx) return CGX_ERR_BAD_ARG;
-    if (kind != CGX_PRECOND_NONE && kind != CGX_PRECOND_JACOBI)
+    if (kind != CGX_PRECOND_NONE && kind != CGX_PRECOND_JACOBI && kind != CGX_PRECOND_PIVCHOL)
         return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner: unknown kind " + std::to_string(kind));
     if (ctx->in_solve) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner: called between cgx_solve_begin and cgx_solve_end");
     // host bookkeeping only: the diagonal is extracted (collectively) by the next cgx_solve_begin
@@ -979,6 +987,47 @@ cgx_status cgx_get_preconditioner_block(const cgx_ctx *ctx, int *block)
 {
     if (!ctx || !block) return CGX_ERR_BAD_ARG;
     *block = ctx->precond_block;
+    return CGX_OK;
+}
+
+cgx_status cgx_set_preconditioner_rank(cgx_ctx *ctx, int rank)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (rank < 1 || rank > CGX_MAX_PRECOND_RANK)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_rank: rank must be 1 ... " + std::to_string(CGX_MAX_PRECOND_RANK) + ", not " +
+                                              std::to_string(rank));
+    if (ctx->in_solve)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_rank: called between cgx_solve_begin and cgx_solve_end");
+    // host bookkeeping only: the factor is made by the next cgx_solve_begin with CGX_PRECOND_PIVCHOL
+    if (rank != ctx->precond_rank) ctx->lr_valid = false;
+    ctx->precond_rank = rank;
+    return CGX_OK;
+}
+
+cgx_status cgx_get_preconditioner_rank(const cgx_ctx *ctx, int *rank)
+{
+    if (!ctx || !rank) return CGX_ERR_BAD_ARG;
+    *rank = ctx->precond_rank;
+    return CGX_OK;
+}
+
+cgx_status cgx_set_preconditioner_shift(cgx_ctx *ctx, double delta)
+{
+    if (!ctx) return CGX_ERR_BAD_ARG;
+    if (!(delta >= 0.0 && delta <= 1.7976931348623157e308))   // NaN, < 0, +inf
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_shift: the shift must be 0 (automatic) or positive and finite");
+    if (ctx->in_solve)
+        return fail(ctx, CGX_ERR_BAD_ARG, "cgx_set_preconditioner_shift: called between cgx_solve_begin and cgx_solve_end");
+    if (delta != ctx->precond_shift) ctx->lr_valid = false;
+    ctx->precond_shift = delta;
+    return CGX_OK;
+}
+
+cgx_status cgx_get_preconditioner_shift(const cgx_ctx *ctx, double *delta_set, double *delta_used)
+{
+    if (!ctx || !delta_set || !delta_used) return CGX_ERR_BAD_ARG;
+    *delta_set = ctx->precond_shift;
+    *delta_used = ctx->lr_valid ? ctx->lr_delta : 0.0;
     return CGX_OK;
 }
 

@@ -89,6 +89,16 @@ struct cgx_ctx {
     bool dinv_valid = false;     // every shard's dinv (block 1) / W (block > 1) holds the checked inverse of the current matrix's
                                  // diagonal (blocks) for precond_block: lowered behind every writer of A and by a new block size
     int *d_jbad = nullptr;       // device word: first row of a diagonal entry Jacobi cannot take (set-up only)
+    // CGX_PRECOND_PIVCHOL (one GPU, dense): the settings belong to the context, the factor to the problem
+    int precond_rank = 32;       // cgx_set_preconditioner_rank: columns of L, read at begin
+    double precond_shift = 0.0;  // cgx_set_preconditioner_shift: 0 = the mean remaining diagonal
+    bool lr_valid = false;       // L, C^-1 and delta hold the factor of the current matrix for precond_rank / precond_shift: lowered
+                                 // behind every writer of A (beside dinv_valid) and by a new rank or shift
+    double lr_delta = 0.0;       // the shift in use, read back behind the set-up
+    double *lr_L = nullptr;      // lr_L_rank x lda doubles, column-major at the matrix pitch
+    int lr_L_rank = 0;
+    double *lr_block = nullptr;  // the set-up's and the loop's work space (cgx::LrWork, carved by lr_work)
+    size_t lr_block_bytes = 0;
     bool res_parked = false;     // the persistent kernel would take this problem, but the preconditioner keeps it on the per-launch path
 
     // RCCL
@@ -299,6 +309,8 @@ int default_parse_threads();   // CGX_MTX_THREADS, else the host's hardware thre
 
 // cgx_precond.cpp
 cgx_status prepare_jacobi(cgx_ctx *ctx);   // inside cgx_solve_begin: refusals, buffers, and once per matrix dinv or the block inverses
+cgx_status prepare_lowrank(cgx_ctx *ctx);  // the same for CGX_PRECOND_PIVCHOL: once per matrix, rank and shift the factor
+cgx::LrWork lr_work(const cgx_ctx *ctx);   // the pieces of ctx->lr_block (null pointers before the first prepare_lowrank)
 
 // cgx_solve.cpp: the exchanges, one iteration, the persistent launches
 cgx_status p2p_allgather(cgx_ctx *ctx, int chan, const double *src, int count, double *dst, long dst_stride, int copy_self,

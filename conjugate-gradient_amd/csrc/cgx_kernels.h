@@ -167,6 +167,47 @@ hipError_t launch_bj_col_slice(const double *A, long lda, int n, int rows, int r
 // bit).  A pivot that is not finite and > 0: *bad = min(*bad, the block's first row).
 hipError_t launch_bj_invert(double *W, long lda, int n, int block, int *bad, hipStream_t s);
 
+// ---- pivoted-Cholesky low-rank preconditioner (cgx_lowrank.hip) -------------------------------------------
+// One GPU, dense storage: A ~ L L^T + delta I, z = (r - L C^-1 L^T r) / delta with C = delta I + L^T L.  L[u * lda + i] is column-
+// major at the matrix pitch, rank x lda doubles, zero in the pad rows.  Rows run in tiles of 256, one workgroup each: lr_grid(n)
+// = ceil(n / 256) workgroups, at most kMaxVectorGrid (n <= 262144: every dense problem that fits the device).
+constexpr int kLrMaxRank = 256;        // = CGX_MAX_PRECOND_RANK
+constexpr int kLrLd = 256;             // pitch of C (rank x rank) and of the partials of t = L^T r (one row per workgroup)
+constexpr int kLrArmed = 0x7f7f7f7f;   // LrHead's ints as the host arms them (hipMemset 0x7f) in front of a set-up
+struct LrHead {
+    double delta;       // the shift in use (k_lr_delta)
+    int bad_step;       // the step whose pivot was not finite and > 0 (kLrArmed: none) ...
+    int bad_row;        // ... and its row; bad_step still armed: the row of a diagonal entry of A that is not finite and > 0
+    int delta_bad;      // delta is not finite and > 0
+    int pad;
+};
+struct LrWork {
+    double *d;          // lda: the remaining diagonal, -inf once a row is chosen
+    double *cand_v;     // 2 x kMaxVectorGrid: per-workgroup (value, index) candidates of the pivot search, ping-pong over the steps
+    int *cand_i;
+    int *piv;           // kLrMaxRank: the pivot rows in the order chosen
+    double *C;          // kLrLd x kLrLd: C, then C^-1 in place (symmetric bit for bit)
+    double *tpart;      // lr_grid(n) x kLrLd: the loop's partials of t
+    LrHead *head;
+};
+int lr_grid(int n);
+// Set-up, all on the device and in stream order: init (diagonal, first candidates), one step per column t = 0 ... rank-1 (pivot
+// = the largest remaining diagonal, ties to the smallest index; column t of L; the next candidates), finish (delta = shift if
+// > 0, else the mean remaining diagonal; C = delta I + L^T L).  The caller then inverts C with launch_bj_invert and reads the
+// head once.  A failed step stops the later ones (they return at once).
+hipError_t launch_lr_init(const double *A, long lda, int n, const LrWork &w, hipStream_t s);
+hipError_t launch_lr_step(const double *A, long lda, int n, int t, double *L, const LrWork &w, hipStream_t s);
+hipError_t launch_lr_finish(const double *L, long lda, int n, int rank, double shift, const LrWork &w, hipStream_t s);
+// The loop: the PCG update kernel (launch_update_xr's Jacobi form on one GPU: fold of tail_count p.Ap partials in K3's order,
+// x, r, the r.r partial at zv.base + zv.S) which also leaves the partials of t; then the apply kernel: z into zv, the r.z
+// partials into its tail.  _init: the partials of t and of r.r from r as it is (set-up from x0).  sc == nullptr: no done flag.
+hipError_t launch_lr_update(int n, const double *p_new, SegView apv, int tail_count, double *x, double *r, Scalars *sc, int parity,
+                            const double *L, long lda, int rank, SegView zv, const LrWork &w, hipStream_t s,
+                            hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr);
+hipError_t launch_lr_update_init(int n, double *r, const double *L, long lda, int rank, SegView zv, const LrWork &w, hipStream_t s);
+hipError_t launch_lr_apply(int n, const double *r, const double *L, long lda, int rank, SegView zv, const LrWork &w,
+                           const Scalars *sc, hipStream_t s);
+
 // v_full[c] = segment value of column c (c < n), 0 for the pad: turns gathered slices into a replicated vector.
 hipError_t launch_unpack_segments(SegView seg, double *v_full, long lda, hipStream_t s);
 

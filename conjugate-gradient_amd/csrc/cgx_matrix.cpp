@@ -70,6 +70,7 @@ cgx_status alloc_csr(cgx_ctx *ctx, Shard &s, long long nnz)
 void plan_csr_shards(cgx_ctx *ctx)
 {
     ctx->dinv_valid = false;
+    ctx->lr_valid = false;
     const int variant = configured_variant(ctx);
     for (auto &s : ctx->shards) s.plan = cgx::plan_csr(s.rows, s.csr.nnz, variant);
 }

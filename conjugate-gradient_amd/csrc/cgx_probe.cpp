@@ -337,6 +337,61 @@ cgx_status cgx_probe_get_precond_blocks(cgx_ctx *ctx, int local_shard, double *W
     return CGX_OK;
 }
 
+// TEST PROBES of the pivoted-Cholesky preconditioner, valid once a cgx_solve_begin with CGX_PRECOND_PIVCHOL
+// has made the factor of the current matrix, rank and shift.
+static cgx_status lowrank_ready(cgx_ctx *ctx, const char *fn)
+{
+    if (ctx->precond != CGX_PRECOND_PIVCHOL || !ctx->lr_valid || !ctx->lr_L || !ctx->lr_block || ctx->lr_L_rank != ctx->precond_rank ||
+        ctx->shards.size() != 1)
+        return fail(ctx, CGX_ERR_BAD_ARG, std::string(fn) + ": no factor (needs a solve begun with CGX_PRECOND_PIVCHOL)");
+    return CGX_OK;
+}
+
+// The pivots in the order chosen (rank ints), L as n rows of rank doubles, and the shift in use.
+cgx_status cgx_probe_get_precond_lowrank(cgx_ctx *ctx, int *pivots, double *L_out, double *delta_used)
+{
+    if (!ctx || !pivots || !L_out || !delta_used) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_get_precond_lowrank: bad argument");
+    CGX_TRY(lowrank_ready(ctx, "cgx_probe_get_precond_lowrank"));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const int rank = ctx->lr_L_rank;
+    const cgx::LrWork w = lr_work(ctx);
+    std::vector<double> l((size_t)rank * ctx->lda);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    HIP_TRY(ctx, hipMemcpy(l.data(), ctx->lr_L, l.size() * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(ctx, hipMemcpy(pivots, w.piv, (size_t)rank * sizeof(int), hipMemcpyDeviceToHost));
+    for (long i = 0; i < ctx->n; ++i)
+        for (int u = 0; u < rank; ++u) L_out[i * rank + u] = l[(size_t)u * ctx->lda + i];
+    *delta_used = ctx->lr_delta;
+    return CGX_OK;
+}
+
+// z = P^-1 r for a caller's vector (n doubles each) through the loop's own kernels: the _init form of the update kernel (the
+// partials of L^T r) and the apply kernel, on buffers of this call.
+cgx_status cgx_probe_precond_apply(cgx_ctx *ctx, const double *r, double *z)
+{
+    if (!ctx || !r || !z) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_precond_apply: bad argument");
+    CGX_TRY(lowrank_ready(ctx, "cgx_probe_precond_apply"));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const cgxi::Shard &s = ctx->shards[0];
+    const cgx::LrWork w = lr_work(ctx);
+    DeviceScratch scratch;
+    double *d_r = nullptr, *d_z = nullptr;
+    const size_t rbytes = (size_t)ctx->lda * sizeof(double), zbytes = (size_t)(s.rv.S + (s.rv.S - s.rv.Sr)) * sizeof(double);
+    HIP_TRY(ctx, scratch.alloc(&d_r, rbytes));
+    HIP_TRY(ctx, scratch.alloc(&d_z, zbytes));
+    cgx::SegView zv = s.rv;
+    zv.base = d_z;
+    hipStream_t st = ctx->stream;
+    HIP_TRY(ctx, hipMemsetAsync(d_r, 0, rbytes, st));
+    HIP_TRY(ctx, hipMemsetAsync(d_z, 0, zbytes, st));
+    HIP_TRY(ctx, hipMemcpyAsync(d_r, r, (size_t)ctx->n * sizeof(double), hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, cgx::launch_lr_update_init(ctx->n, d_r, ctx->lr_L, ctx->lda, ctx->lr_L_rank, zv, w, st));
+    HIP_TRY(ctx, cgx::launch_lr_apply(ctx->n, d_r, ctx->lr_L, ctx->lda, ctx->lr_L_rank, zv, w, nullptr, st));
+    HIP_TRY(ctx, hipMemcpyAsync(z, d_z, (size_t)ctx->n * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return CGX_OK;
+}
+
 // TEST PROBE: overwrite the dense row block of every local shard of the CURRENT problem with the hash matrix of
 // cgx_kernels.h (hash_entry): element (i, j) = a pure function of (seed, i, j) in [-1, 1), filled on the device.  The
 // geometry (n, partition, pitch, K1 plan) stays what the problem set before it defined; b and max_iter are untouched.

@@ -186,7 +186,7 @@ static cgx_status run_gemv_fused(cgx_ctx *ctx, Shard &s, int k)
         m1 = e1;
         e0 = e1 = nullptr;
     }
-    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;   // p = z + beta p_old: K1 reads z where it reads r otherwise
+    const bool pc = ctx->precond != CGX_PRECOND_NONE;   // p = z + beta p_old: K1 reads z where it reads r otherwise
     if (ctx->csr)
         HIP_TRY(ctx, cgx::launch_spmv_csr_fused(s.plan, s.csr, s.rows, s.row0, ctx->lda, s.p[k & 1], s.p[(k + 1) & 1], pc ? s.zv : s.rv,
                                                 s.Ap(), s.k1_part(), s.sc, k, ctx->tol, ctx->stream, e0, e1, pc));
@@ -255,6 +255,18 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
     const bool bj = pc && ctx->precond_block > 1;   // block Jacobi: the update kernel's block form (never with the exchange inside)
     // tail of iteration k-1 (cg.cc:117-132) + GEMV and p.Ap partials of iteration k (cg.cc:100-105)
     for (auto &s : ctx->shards) CGX_TRY(run_gemv_fused(ctx, s, k));
+    if (ctx->precond == CGX_PRECOND_PIVCHOL) {
+        // one GPU, dense (prepare_lowrank): the update kernel that also leaves the partials of L^T r, then z = P^-1 r (section 15)
+        Shard &s = ctx->shards[0];
+        const cgx::LrWork w = lr_work(ctx);
+        hipEvent_t u0, u1;
+        CGX_TRY(take_update_events(ctx, &u0, &u1));
+        const int count = s.plan.variant == 6 ? cgx::plan_partials(s.plan) : ctx->npart;
+        HIP_TRY(ctx, cgx::launch_lr_update(ctx->n, s.p[(k + 1) & 1], s.apv, count, s.x, s.rv.base, s.sc, k & 1, ctx->lr_L, ctx->lda,
+                                           ctx->lr_L_rank, s.zv, w, st, u0, u1));
+        HIP_TRY(ctx, cgx::launch_lr_apply(ctx->n, s.rv.base, ctx->lr_L, ctx->lda, ctx->lr_L_rank, s.zv, w, s.sc, st));
+        return CGX_OK;
+    }
     if (ctx->cfg.comm_mode == CGX_COMM_P2P && !ctx->cfg.p2p_separate_exchange) {
         // direct peer exchange folded into K3: the iteration is two kernels, no collective launch at all
         Shard &s = ctx->shards[0];
@@ -609,7 +621,9 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
     if (!ctx->have_matrix || !ctx->have_b) return fail(ctx, CGX_ERR_BAD_ARG, "matrix and source term must be set before solve");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
+    const bool lr = ctx->precond == CGX_PRECOND_PIVCHOL;
     if (pc) CGX_TRY(prepare_jacobi(ctx));
+    if (lr) CGX_TRY(prepare_lowrank(ctx));
     ctx->t_begin = wall_now();
     ctx->t_loop = 0;
     ctx->k = 0;
@@ -658,6 +672,12 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
         HIP_TRY(ctx, cgx::launch_init_residual(n, s.b_full, s.apv, s.rv, s.partials, st,            // cg.cc:82 (Jacobi: and z0)
                                                pc ? s.dinv : nullptr, s.zv, pc && ctx->precond_block > 1 ? s.W : nullptr,
                                                ctx->precond_block, ctx->lda));
+    if (lr) {   // z0 = P^-1 r0 behind the plain initial residual: the partials of L^T r0 and of r0.r0, then the apply kernel
+        Shard &s = ctx->shards[0];
+        const cgx::LrWork w = lr_work(ctx);
+        HIP_TRY(ctx, cgx::launch_lr_update_init(n, s.rv.base, ctx->lr_L, ctx->lda, ctx->lr_L_rank, s.zv, w, st));
+        HIP_TRY(ctx, cgx::launch_lr_apply(n, s.rv.base, ctx->lr_L, ctx->lda, ctx->lr_L_rank, s.zv, w, nullptr, st));
+    }
     for (auto &s : ctx->shards) {
         // p_old of iteration 0 is 0, so K1(0) forms p = r + 0*0 = r  (p_sub = r_sub, cg.cc:85; Jacobi: p0 = z0)
         HIP_TRY(ctx, hipMemsetAsync(s.p[0], 0, vec_bytes, st));
@@ -710,7 +730,7 @@ cgx_status cgx_solve_end(cgx_ctx *ctx, double *x, cgx_result *res)
     // The convergence test of the last enqueued iteration is normally done by the NEXT K1; when the loop
     // ran out there is none, so close it here (cg.cc:117-121,132).
     // (the LDS-resident kernel has made that test itself; with no iteration done the state is the per-launch path's)
-    const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
+    const bool pc = ctx->precond != CGX_PRECOND_NONE;   // either kind: z's layout, r.z in rs[], r.r in rr[]
     if (!ctx->resident || ctx->k == 0) {
         for (auto &s : ctx->shards) HIP_TRY(ctx, cgx::launch_close_iteration(s.sc, pc ? s.zv : s.rv, ctx->k, ctx->tol, st, pc));
         CGX_TRY(read_flags_sync(ctx));

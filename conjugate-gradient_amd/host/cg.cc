@@ -39,6 +39,8 @@ void CGSolver::tolerance(double tolerance) { check(cgx_set_tolerance(m_ctx, tole
 
 void CGSolver::set_preconditioner(int kind) { check(cgx_set_preconditioner(m_ctx, kind), "set_preconditioner"); }
 void CGSolver::set_preconditioner_block(int block) { check(cgx_set_preconditioner_block(m_ctx, block), "set_preconditioner_block"); }
+void CGSolver::set_preconditioner_rank(int rank) { check(cgx_set_preconditioner_rank(m_ctx, rank), "set_preconditioner_rank"); }
+void CGSolver::set_preconditioner_shift(double delta) { check(cgx_set_preconditioner_shift(m_ctx, delta), "set_preconditioner_shift"); }
 
 int CGSolver::m() const
 {

@@ -45,9 +45,11 @@ public:
     void tolerance(double tolerance);
 
     // additions
-    /// CGX_PRECOND_NONE or CGX_PRECOND_JACOBI (include/cgx.h): takes effect at the next solve
+    /// CGX_PRECOND_NONE, CGX_PRECOND_JACOBI or CGX_PRECOND_PIVCHOL (include/cgx.h): takes effect at the next solve
     void set_preconditioner(int kind);
     void set_preconditioner_block(int block);   // 1 = point Jacobi; 2 ... 256 = block Jacobi (cgx_set_preconditioner_block)
+    void set_preconditioner_rank(int rank);     // CGX_PRECOND_PIVCHOL: columns of the factor, 1 ... 256 (cgx_set_preconditioner_rank)
+    void set_preconditioner_shift(double delta);   // ... and its shift, 0 = automatic (cgx_set_preconditioner_shift)
     /// multi-shift CG (include/cgx.h cgx_solve_shifted): X[j * n() + i] = solution i of (A + shifts[j] I) x = b from a zero guess,
     /// one pass over A per iteration for all shifts; the per-shift results are kept (shift_results), last_result() is shift 0's
     void solve_shifted(const std::vector<double> &shifts, std::vector<double> &X);

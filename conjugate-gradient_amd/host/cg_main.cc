@@ -20,6 +20,8 @@
 // `--shifts s0,s1,...` (NOT a reference mode) runs multi-shift CG instead of the plain solve (include/cgx.h cgx_solve_shifted): the
 // systems (A + s_j I) x = b for up to 16 shifts s_j >= 0 from one Krylov sequence, one pass over A per iteration.  The timing line
 // in OUTFILE is written as ever; one line per shift follows on stdout.  One GPU, dense or --csr, no --jacobi.
+// `--pivchol K [--pivchol-shift D]` (NOT a reference mode) solves with the rank-K pivoted-Cholesky preconditioner plus shift
+// (include/cgx.h CGX_PRECOND_PIVCHOL; D = 0 or absent: the automatic shift): one GPU, dense storage, not with --jacobi.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -146,6 +148,10 @@ int usage(const char *prog)
               << "                                  sqrt(r.r) < tol as without it; dense or CSR storage, per-launch loop)\n"
               << "         --jacobi-block B         implies --jacobi: block Jacobi with the B x B diagonal blocks, B = 1, 2, 4,\n"
               << "                                  ..., 256 (1 = --jacobi; not with --transport p2p)\n"
+              << "         --pivchol K              opt-in, not in the reference: CG preconditioned with a rank-K pivoted-Cholesky\n"
+              << "                                  factor plus shift (K = 1 ... 256; for dense SPD matrices whose off-diagonal\n"
+              << "                                  mass is global; one GPU, dense storage, not with --jacobi)\n"
+              << "         --pivchol-shift D        with --pivchol: the shift (default 0 = the mean remaining diagonal)\n"
               << "         --shifts s0,s1,...       opt-in, not in the reference: solve (A + s I) x = b for up to 16 shifts s >= 0 in\n"
               << "                                  one Krylov sequence (multi-shift CG) instead of the plain solve; one GPU, dense\n"
               << "                                  or --csr, not with --jacobi; prints one line per shift\n"
@@ -168,6 +174,9 @@ int main(int argc, char **argv)
     std::string transport = "auto";
     std::string test_hang;   // --test-hang-stage
     int jacobi_block = 1;
+    int pivchol = 0;             // --pivchol K (0: off)
+    double pivchol_shift = 0.0;
+    bool have_pivchol_shift = false;
     std::vector<double> shifts;
     bool shifted = false;
     double wireup_timeout = 120.0;
@@ -184,6 +193,22 @@ int main(int argc, char **argv)
         else if (a == "--jacobi-block" && i + 1 < argc) {
             jacobi = true;
             jacobi_block = atoi(argv[++i]);
+        }
+        else if (a == "--pivchol" && i + 1 < argc) {
+            pivchol = atoi(argv[++i]);
+            if (pivchol < 1 || pivchol > CGX_MAX_PRECOND_RANK) {
+                std::cerr << argv[0] << ": --pivchol takes a rank 1 ... " << CGX_MAX_PRECOND_RANK << ", not '" << argv[i] << "'\n";
+                return usage(argv[0]);
+            }
+        }
+        else if (a == "--pivchol-shift" && i + 1 < argc) {
+            char *end = nullptr;
+            pivchol_shift = strtod(argv[++i], &end);
+            have_pivchol_shift = true;
+            if (end == argv[i] || *end != '\0' || !(pivchol_shift >= 0.0) || !(pivchol_shift <= 1.7976931348623157e308)) {
+                std::cerr << argv[0] << ": --pivchol-shift takes 0 (automatic) or a positive finite number, not '" << argv[i] << "'\n";
+                return usage(argv[0]);
+            }
         }
         else if (a == "--shifts" && i + 1 < argc) {
             shifted = true;
@@ -215,6 +240,14 @@ int main(int argc, char **argv)
     if (pos.empty()) return usage(argv[0]);   // cg_main.cc:22-26 (returns 1)
     if (csr && banded) {
         std::cerr << argv[0] << ": --csr and --banded are two storages: give one of them\n";
+        return usage(argv[0]);
+    }
+    if (have_pivchol_shift && !pivchol) {
+        std::cerr << argv[0] << ": --pivchol-shift belongs to --pivchol K\n";
+        return usage(argv[0]);
+    }
+    if (pivchol && jacobi) {
+        std::cerr << argv[0] << ": --pivchol and --jacobi are two preconditioners: give one of them\n";
         return usage(argv[0]);
     }
     if (ngpu < 1) ngpu = 1;
@@ -428,6 +461,11 @@ int main(int argc, char **argv)
         CGSolver &solver = *holder;
         if (jacobi) solver.set_preconditioner(CGX_PRECOND_JACOBI);   // every rank, before the first solve
         if (jacobi_block != 1) solver.set_preconditioner_block(jacobi_block);
+        if (pivchol) {
+            solver.set_preconditioner(CGX_PRECOND_PIVCHOL);
+            solver.set_preconditioner_rank(pivchol);
+            solver.set_preconditioner_shift(pivchol_shift);
+        }
 
         if (gen_form) solver.generate_lap2d_matrix(gen_n);   // cg_main.cc:31
         else solver.read_matrix(pos[0]);                     // code/CUDA/cg_main.cc:37
@@ -493,6 +531,11 @@ int main(int argc, char **argv)
                 std::cerr << " persistent_launches_redone_per_launch=" << rec[8];
                 if (jacobi) std::cerr << " precond=jacobi";   // only when set: the plain line stays as it was
                 if (jacobi_block != 1) std::cerr << " block=" << jacobi_block;
+                if (pivchol) {
+                    double set = 0, used = 0;
+                    (void)cgx_get_preconditioner_shift(solver.context(), &set, &used);
+                    std::cerr << " precond=pivchol rank=" << pivchol << " shift=" << used << " converged=" << r.converged;
+                }
                 std::cerr << std::endl;
             }
         }

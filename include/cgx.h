@@ -273,6 +273,30 @@ cgx_status  cgx_get_preconditioner(const cgx_ctx *ctx, int *kind);
  * (p2p_separate_exchange = 1 is supported). */
 cgx_status  cgx_set_preconditioner_block(cgx_ctx *ctx, int block);
 cgx_status  cgx_get_preconditioner_block(const cgx_ctx *ctx, int *block);
+/* CGX_PRECOND_PIVCHOL: a rank-k partial Cholesky factor with diagonal pivoting plus a shift, A ~ L L^T +
+ * delta I, applied through the Woodbury identity: z = (r - L (delta I + L^T L)^-1 L^T r) / delta.  For dense SPD matrices whose
+ * diagonal is nearly constant and whose off-diagonal mass is global (kernel / covariance matrices K + sigma^2 I), where Jacobi
+ * does nothing.  The recurrence, the stopping test and every reported field are those of CGX_PRECOND_JACOBI above.  One GPU and
+ * dense storage: more than one rank or a comm_mode other than CGX_COMM_SELF, CGX_MATRIX_BANDED, CGX_MATRIX_CSR and gemv_variant
+ * 40000 / 50000 and a K1 shape with split columns (gemv_variant ending in 3, 4 or 5) give CGX_ERR_UNSUPPORTED at cgx_solve_begin
+ * (cgx_solve_multi and cgx_solve_shifted refuse any preconditioner).
+ * An enumerator, not a macro: the CGX_PRECOND_* macros are the two Jacobi-era kinds.
+ * rank: the columns of L, 1 ... CGX_MAX_PRECOND_RANK (default 32); rank > n is CGX_ERR_BAD_ARG at begin.  shift: delta; 0 (the
+ * default) = automatic, the mean of the diagonal of A - L L^T that remains after `rank` steps, summed in a fixed order; a
+ * positive finite value is used as given; anything else is CGX_ERR_BAD_ARG.  *delta_used = the shift of the factor in use, 0
+ * until a begin has made one for the current matrix, rank and shift.  Both settings belong to the context, survive new matrices,
+ * start no GPU work, take effect at the next begin (between begin and end: CGX_ERR_BAD_ARG) and are used only while the kind is
+ * CGX_PRECOND_PIVCHOL.  That begin makes the factor on the device once per matrix, rank and shift: at step t the pivot is the
+ * not yet chosen row with the largest remaining diagonal (ties: the smallest index), so the pivot sequence is deterministic.  A
+ * diagonal entry or a pivot that is not finite and > 0 (the matrix is not positive definite), or a resulting shift that is not
+ * finite and > 0, gives CGX_ERR_BAD_ARG (step and row in cgx_last_error) and leaves the context usable.  L takes 8 * rank * lda
+ * bytes of device memory; a failed allocation is CGX_ERR_OOM (the size in cgx_last_error). */
+enum { CGX_PRECOND_PIVCHOL = 2 };
+#define CGX_MAX_PRECOND_RANK 256
+cgx_status  cgx_set_preconditioner_rank(cgx_ctx *ctx, int rank);
+cgx_status  cgx_get_preconditioner_rank(const cgx_ctx *ctx, int *rank);
+cgx_status  cgx_set_preconditioner_shift(cgx_ctx *ctx, double delta);
+cgx_status  cgx_get_preconditioner_shift(const cgx_ctx *ctx, double *delta_set, double *delta_used);
 /* Storage of local shard `local_shard`: *format = cgx_matrix_format; banded: *ndiag and offsets[0..*ndiag)
  * (column minus row, ascending; room for CGX_MAX_DIAGONALS ints or NULL); *matrix_bytes = device bytes of the block. */
 cgx_status  cgx_get_matrix_format(const cgx_ctx *ctx, int local_shard, int *format, int *ndiag, int *offsets,
@@ -410,6 +434,12 @@ cgx_status  cgx_probe_fill_matrix_hash(cgx_ctx *ctx, unsigned long long seed, in
  * (D_b^-1)(i, s(i) + t) with s(i) = i - i mod block (0 outside a truncated last block).  Valid after a cgx_solve_begin with a
  * block size > 1; otherwise CGX_ERR_BAD_ARG. */
 cgx_status  cgx_probe_get_precond_blocks(cgx_ctx *ctx, int local_shard, double *W_out);
+/* TEST ONLY: the factor of CGX_PRECOND_PIVCHOL: pivots[0 .. rank) = the pivot rows in the order chosen, L_out = n rows of rank
+ * doubles (row i, entry t = L[i][t]), *delta_used = the shift in use.  cgx_probe_precond_apply: z = P^-1 r for a caller's vector
+ * (n doubles each) through the device code the loop runs.  Both are valid after a cgx_solve_begin with the kind set; otherwise
+ * CGX_ERR_BAD_ARG. */
+cgx_status  cgx_probe_get_precond_lowrank(cgx_ctx *ctx, int *pivots, double *L_out, double *delta_used);
+cgx_status  cgx_probe_precond_apply(cgx_ctx *ctx, const double *r, double *z);
 /* Copy this shard's device row block (rows x n, dense, row-major) back to the host (banded storage is expanded). */
 cgx_status  cgx_probe_get_matrix_rows(cgx_ctx *ctx, int local_shard, double *A_out, int *row0, int *rows);
 
