@@ -103,6 +103,48 @@ __device__ __forceinline__ double block_sum(double v, double *lds /* >= WAVES do
     return s;
 }
 
+// ------------------------------------------------------------------------------------------------
+// p.Ap = sum of every K1 workgroup partial of every rank (cblas_ddot + MPI_Allreduce, cg.cc:105-106): the thread's share, to be
+// finished by block_sum<4>.  Every workgroup of every rank (K3 in all its forms, the low-rank, multi-right-hand-side and
+// multi-shift updates) folds the same partials in the same fixed order: bit-identical everywhere.  The partials of rank q are
+// the `count` doubles at tails + q * S; one contiguous run is nranks == 1.  All 256 threads of the workgroup.
+// ------------------------------------------------------------------------------------------------
+// One row per thread (k_update_xr): one flat index over (rank, partial).  With a few partials per rank (the chunk partials of a
+// multi-GPU run: n/512 in all) every thread has at most one or two loads, all in flight together -- a loop over the ranks with
+// one load each was a chain of P dependent round trips (5.9 us at P = 8 against 4.8 at P = 2 and 4, round 3).
+__device__ __forceinline__ double fold_pap(const double *tails, int nranks, int S, int count)
+{
+    const int total = nranks * count;
+    auto at = [&](int f) {
+        if (nranks == 1) return tails[f];
+        const int q = f / count;
+        return tails[(long)q * S + (f - q * count)];
+    };
+    double cs = 0.0;
+    for (int f = threadIdx.x; f < total; f += 4 * 256) {   // four independent loads in flight (clamped, not branched around)
+        double a[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const int g = f + u * 256;
+            const double val = at(g < total ? g : total - 1);
+            a[u] = g < total ? val : 0.0;
+        }
+        cs += (a[0] + a[1]) + (a[2] + a[3]);
+    }
+    return cs;
+}
+
+// Rows strided over the workgroups (k_update_xr_strided): a lane-strided sum, rank by rank.
+__device__ __forceinline__ double fold_pap_strided(const double *tails, int nranks, int S, int count)
+{
+    double cs = 0.0;
+    for (int q = 0; q < nranks; ++q) {
+        const double *tail = tails + (long)q * S;
+        for (int j = threadIdx.x; j < count; j += 256) cs += tail[j];
+    }
+    return cs;
+}
+
 // The tag of an epoch: 1 + (epoch mod (2^32 - 1)), i.e. 1 ... 2^32 - 1, never 0; consecutive epochs of one parity (e-2, e)
 // always differ, and two epochs share a tag only 2^32 - 1 apart.
 __device__ __forceinline__ unsigned p2p_tag(unsigned long long epoch)
@@ -337,9 +379,10 @@ __device__ __forceinline__ IterHead iteration_head_t(Scalars *sc, const SegView 
     return head_finish_t<PRE>(hl, sc, sv, k, tol);
 }
 
-// One row of the Jacobi update, the same function in every Jacobi update kernel (k_update_xr_pc, k_update_xr_strided_pc,
-// k_pcg_update_p2p, k_init_residual_pc), so that every transport produces the same bits: r_new = r - alpha Ap, z = dinv r_new, and the row's terms
-// of r.r and r.z.
+// One row of the Jacobi update, the same function wherever z = dinv r is formed -- the Jacobi kind of K3's three bodies
+// (update_xr_tile, update_xr_strided, init_residual_rows in cgx_kernels.hip: k_update_xr_pc, k_update_xr_strided_pc,
+// k_init_residual_pc) and k_pcg_update_p2p -- so that every transport produces the same bits: r_new = r - alpha Ap,
+// z = dinv r_new, and the row's terms of r.r and r.z.  (The block kind fills the same PcRow from its chain: bj_row.)
 struct PcRow {
     double r, z, rr, rz;
 };

@@ -121,13 +121,22 @@ hipError_t launch_prefold_ap(const double *parts, int split, long stride, int ro
 // K3: p.Ap = fixed-order sum over all ranks q of the tail_count doubles at tail_off of segment q's tail;
 // alpha = rsold / max(p.Ap, rsold*1e-14); x_sub += alpha p_sub (own rows); r -= alpha Ap for ALL n rows (r is
 // replicated, rv = [r (lda) | one r.r partial per K3 workgroup]); the next K1's head folds the partials.  cg.cc:105-116.
-// dinv != nullptr: the Jacobi form -- also z = dinv * r_new into zv (the layout of rv) and, per workgroup, the r.z partial
-// into zv's tail and the r.r partial behind it (zv.base + zv.S); alpha then uses rho = r.z (sc->rs).
+// How K3 and the residual set-up make z from r_new (default: they make none).  kPrecJacobi: also z = dinv * r_new into zv (the
+// layout of rv) and, per workgroup, the r.z partial into zv's tail and the r.r partial behind it (zv.base + zv.S); alpha then
+// uses rho = r.z (sc->rs).  kPrecBlock: z = D_b^-1 r_new from W (block, lda: see "block Jacobi" below), stored like Jacobi's.
+enum PrecKind { kPrecNone = 0, kPrecJacobi = 1, kPrecBlock = 2 };
+struct UpdatePrecond {
+    PrecKind kind = kPrecNone;
+    const double *dinv = nullptr;
+    const double *W = nullptr;
+    int block = 1;
+    long lda = 0;
+    SegView zv{};
+};
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s,
                             hipEvent_t e_start = nullptr, hipEvent_t e_stop = nullptr,   // optional: bound to the dispatch
-                            const double *dinv = nullptr, SegView zv = SegView{},
-                            const double *W = nullptr, int block = 1, long lda = 0);   // W != nullptr: block Jacobi, see below
+                            const UpdatePrecond &pc = UpdatePrecond{});
 int update_xr_grid(int count);   // ceil(count/256), at most kMaxVectorGrid (above that the kernels stride over the rows)
 constexpr int kMaxVectorGrid = 1024;
 
@@ -140,10 +149,9 @@ hipError_t launch_reduce_partials(const double *partials, int n, double *out, hi
 hipError_t launch_reduce_partials3(const double *partials, int n, double *out3, hipStream_t s);
 
 // Initial residual (cg.cc:79-85): r = b - Ap for all n rows (Ap from the gathered segments); rv tail[wg] = sum r_i^2.
-// dinv != nullptr (Jacobi): also z0 = dinv * r0 into zv, the r.z partials in zv's tail and the r.r partials behind them.
+// Preconditioned (pc.kind): also z0 from r0 into pc.zv, the r.z partials in its tail and the r.r partials behind them.
 hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
-                                const double *dinv = nullptr, SegView zv = SegView{}, const double *W = nullptr, int block = 1,
-                                long lda = 0);
+                                const UpdatePrecond &pc = UpdatePrecond{});
 
 // ---- Jacobi -------------------------------------------------------------------------------------------
 // dst[i] = A(row0 + i, row0 + i) for the shard's rows (dst: its Ap slice, which the segment exchange then gathers).
@@ -155,7 +163,7 @@ hipError_t launch_jacobi_dinv(SegView apv, int n, long lda, double *dinv, int *b
 // ---- block Jacobi -------------------------------------------------------------------------------------
 // z = D_b^-1 r, D_b = the block x block diagonal blocks of A over the global ranges [j block, min((j+1) block, n)).  The inverses:
 // W[t * lda + i] = (D_b^-1)(i, s(i) + t), s(i) = i - i mod block; block x lda doubles per shard, replicated like dinv, zero
-// outside the truncated last block and in the pad rows.  launch_update_xr / launch_init_residual with W != nullptr run the
+// outside the truncated last block and in the pad rows.  launch_update_xr / launch_init_residual with kind kPrecBlock run the
 // block forms: z_i = one fma chain from +0.0 over t ascending, the same in every kernel.
 constexpr int kBjMaxBlock = 256;   // every allowed block divides the 256 rows of an update workgroup
 constexpr int kBjLdsBlock = 128;   // up to here the inversion works on a copy of the block in LDS

@@ -446,13 +446,108 @@ __global__ __launch_bounds__(256) void k_prefold_ap(const double *__restrict__ p
 // K3: x_sub += alpha p_sub ; r -= alpha Ap (all n rows) ; r.r          (cg.cc:106-116)
 // apv: the gathered segments [Ap slice | tail] of all ranks; the p.Ap partials of rank q are the
 // tail_count doubles at tail_off of its segment.  rv: the replicated r, [r (lda) | scalars].
+//
+// Nine entry points over three bodies.  The bodies (update_xr_tile: one row per thread; update_xr_strided: more than
+// 256 * kMaxVectorGrid rows; init_residual_rows: the set-up in front of the loop) are templates on how z is made from r_new:
+//   kPcNone    k_update_xr, k_update_xr_strided, k_init_residual: no z; the workgroup's r.r partial goes behind r.
+//   kPcJacobi  ..._pc: alpha = rho / p.Ap (rho = r.z in sc->rs) and, per row, z = dinv r_new (pc_row);
+//              dinv[i] is loaded with the other loads ahead of the first wait.  zv: the replicated z, laid out as rv; the
+//              workgroup's r.z partial goes into its tail, the r.r partial behind that (pc_store_partials), in the same
+//              order as the plain r.r partials.
+//   kPcBlock   ..._bj<B>: z = D_b^-1 r with the B x B diagonal blocks of A inverted once per matrix.
+//              W[t * lda + i] = (D_b^-1)(i, s(i) + t), s(i) = i - i mod B: replicated like dinv, zero outside the (truncated
+//              last) block and in the pad rows.  A workgroup owns 256 consecutive global rows starting at a multiple of 256,
+//              and B divides 256, so a tile holds whole blocks: its 256 values of r_new go to LDS and thread i runs ONE fma
+//              chain from +0.0 over t = 0 ... B-1 ascending, acc = fma(W[t][i], r_new[s(i) + t], acc) -- the same chain in
+//              every body, so z_i depends on (i, B) only.  (Terms beyond a truncated block are fma(0, 0, acc) = acc.)
+//              The same loads, the same alpha, the same partials as the Jacobi kind.
+// Everything else -- the loads ahead of the first wait, the fold of p.Ap (fold_pap, cgx_device.h), alpha, x += alpha p, the
+// block_sum calls -- is written once per body, so the kinds agree bit for bit by construction.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_update_xr(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                    SegView apv, int tail_off, int tail_count,
-                                                    double *__restrict__ x, SegView rv, Scalars *sc, int parity,
-                                                    double *partials)
+enum { kPcNone = kPrecNone, kPcJacobi = kPrecJacobi, kPcBlock = kPrecBlock };
+
+constexpr int kBjEarly = 16;   // W loads issued ahead of the first wait (they do not depend on alpha); the rest in steps of 8
+
+template <int B>
+struct BjEarly {
+    static constexpr int N = B < kBjEarly ? B : kBjEarly;
+    double w[N];
+};
+
+// the thread's first W entries; `row` is clamped by the caller to a row that exists (a pad row's z is never stored)
+template <int B>
+__device__ __forceinline__ BjEarly<B> bj_issue(const double *__restrict__ W, long lda, long row)
 {
-    __shared__ double lds[4];
+    BjEarly<B> e;
+#pragma unroll
+    for (int t = 0; t < BjEarly<B>::N; ++t) e.w[t] = W[(long)t * lda + row];
+    return e;
+}
+
+// z_i from the tile's r_new in LDS (rl[0 .. 256), written and barriered by the caller)
+template <int B>
+__device__ __forceinline__ double bj_chain(const BjEarly<B> &e, const double *__restrict__ W, long lda, long row, const double *rl)
+{
+    const double *rb = rl + ((int)threadIdx.x & ~(B - 1));   // the block's start inside the tile: an LDS broadcast per quarter wave
+    double acc = 0.0;
+#pragma unroll
+    for (int t = 0; t < BjEarly<B>::N; ++t) acc = fma(e.w[t], rb[t], acc);
+    if constexpr (B > kBjEarly) {
+        const double *wp = W + (long)kBjEarly * lda + row;
+#pragma unroll 1   // one running pointer: unrolled, the B - 16 row offsets t * lda spill scalar registers
+        for (int t0 = kBjEarly; t0 < B; t0 += 8, wp += 8 * lda) {
+            double w[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) w[u] = wp[(long)u * lda];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) acc = fma(w[u], rb[t0 + u], acc);
+        }
+    }
+    return acc;
+}
+
+__device__ __forceinline__ PcRow bj_row(double r_new, double z)
+{
+    PcRow o;
+    o.r = r_new;
+    o.z = z;
+    o.rr = r_new * r_new;
+    o.rz = r_new * z;
+    return o;
+}
+
+// Row i of any kind: r[i] (and z[i]) stored, the row's terms of r.r (and r.z) returned.  zd: dinv[i] (Jacobi) or z_i itself
+// (block); plain: unused, and what is made from it is dropped.
+template <int KIND>
+__device__ __forceinline__ PcRow store_row(double r_new, double zd, long i, double *r, const SegView &zv)
+{
+    const PcRow o = KIND == kPcBlock ? bj_row(r_new, zd) : pc_row(r_new, zd);
+    r[i] = o.r;
+    if constexpr (KIND != kPcNone) zv.base[i] = o.z;
+    return o;
+}
+
+// One r.r partial per workgroup behind r (plain: the same slots for K3 and the set-up, folded by the next K1's head,
+// cg.cc:91-92 for K1(0)), or the r.z / r.r pair behind z.
+template <int KIND>
+__device__ __forceinline__ void store_partials(const SegView &rv, const SegView &zv, double rr, double rz, double *lds)
+{
+    rr = block_sum<4>(rr, lds);
+    if constexpr (KIND == kPcNone) {
+        if (threadIdx.x == 0) rv.base[rv.Sr + blockIdx.x] = rr;
+    } else {
+        rz = block_sum<4>(rz, lds);
+        if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+    }
+}
+
+// One row per thread.  pre: dinv (Jacobi) or W (block); lds: 4 doubles; rl: 256 doubles (block only).
+template <int KIND, int B>
+__device__ __forceinline__ void update_xr_tile(int n, int rows, int row0, const double *__restrict__ p_new, const SegView &apv,
+                                               int tail_off, int tail_count, double *__restrict__ x, const SegView &rv,
+                                               Scalars *sc, int parity, const double *__restrict__ pre, long lda,
+                                               const SegView &zv, double *lds, double *rl)
+{
     double *r = rv.base;
     // Issue every load this thread needs before the first wait: the kernel is a chain of ~1 us memory round
     // trips (flag, partials, vectors), so they are overlapped instead of serialised.
@@ -461,100 +556,186 @@ __global__ __launch_bounds__(256) void k_update_xr(int n, int rows, int row0, co
     const int i = blockIdx.x * 256 + threadIdx.x;                     // global row
     const int li = i - row0;
     const bool in = i < n, own = in && li >= 0 && li < rows;
-    double ap_i = 0.0, r_i = 0.0, p_i = 0.0, x_i = 0.0;
-    if (in) { ap_i = seg_load(apv, i); r_i = r[i]; }
-    if (own) { p_i = p_new[i]; x_i = x[li]; }
-    // p.Ap = sum of every K1 workgroup partial of every rank (cblas_ddot + MPI_Allreduce, cg.cc:105-106), folded
-    // in one fixed order by every workgroup of every rank: bit-identical everywhere.
-    // One flat index over (rank, partial): with a few partials per rank (the chunk partials of a multi-GPU run: n/512 in
-    // all) every thread has at most one or two loads, all in flight together -- a loop over the ranks with one load each was
-    // a chain of P dependent round trips (5.9 us at P = 8 against 4.8 at P = 2 and 4, round 3).
-    double cs = 0.0;
-    {
-        const int total = apv.nranks * tail_count;
-        const double *tails = apv.base + apv.Sr + tail_off;
-        auto at = [&](int f) {
-            if (apv.nranks == 1) return tails[f];
-            const int q = f / tail_count;
-            return tails[(long)q * apv.S + (f - q * tail_count)];
-        };
-        for (int f = threadIdx.x; f < total; f += 4 * 256) {   // four independent loads in flight (clamped, not branched around)
-            double a[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int g = f + u * 256;
-                const double val = at(g < total ? g : total - 1);
-                a[u] = g < total ? val : 0.0;
-            }
-            cs += (a[0] + a[1]) + (a[2] + a[3]);
-        }
+    double ap_i = 0.0, r_i = 0.0, zd = 0.0, p_i = 0.0, x_i = 0.0;   // zd: store_row's
+    if (in) {
+        ap_i = seg_load(apv, i);
+        r_i = r[i];
+        if constexpr (KIND == kPcJacobi) zd = pre[i];
     }
+    if (own) { p_i = p_new[i]; x_i = x[li]; }
+    const long wrow = in ? i : 0;
+    BjEarly<B> e;
+    if constexpr (KIND == kPcBlock) e = bj_issue<B>(pre, lda, wrow);
+    const double cs = fold_pap(apv.base + apv.Sr + tail_off, apv.nranks, apv.S, tail_count);
     if (done) return;   // converged earlier (uniform over the grid): nothing is written
     const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);             // cg.cc:107
-    double rr = 0.0;
+    const double alpha = safeguarded_alpha(rsold, conj);             // cg.cc:107 (Jacobi: rho / p.Ap, the bound relative to rho)
+    const double rn = in ? fma(-alpha, ap_i, r_i) : 0.0;             // cg.cc:113, for every row (r is replicated)
+    if constexpr (KIND == kPcBlock) {                                // rows past n: exactly 0, they meet W's zeros only
+        rl[threadIdx.x] = rn;
+        __syncthreads();
+        zd = bj_chain<B>(e, pre, lda, wrow, rl);
+    }
+    double rr = 0.0, rz = 0.0;
     if (in) {
-        const double rn = fma(-alpha, ap_i, r_i);                     // cg.cc:113, for every row (r is replicated)
-        r[i] = rn;
-        rr = rn * rn;                                                 // cg.cc:116
+        const PcRow o = store_row<KIND>(rn, zd, i, r, zv);
+        rr = o.rr;                                                    // cg.cc:116
+        rz = o.rz;
     }
     if (own) x[li] = fma(alpha, p_i, x_i);                            // cg.cc:110, own rows only
-    rr = block_sum<4>(rr, lds);
-    if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;   // one r.r partial per workgroup, folded by the next K1's head
+    store_partials<KIND>(rv, zv, rr, rz, lds);
 }
 
-// K3, Jacobi form: k_update_xr with alpha = rho / p.Ap (rho = r.z in sc->rs) and, per row, z = dinv r_new (pc_update_row);
-// dinv[i] is loaded with the other loads ahead of the first wait.  zv: the replicated z, laid out as rv; the workgroup's r.z
-// partial goes into its tail, the r.r partial behind that (pc_store_partials), in the same order as the plain r.r partials.
+// The rows of a workgroup that strides over the vector: r_new = r_new_of(i), z by KIND, both stored, the terms of r.r and
+// r.z summed, then after(i).  The block kind strides over whole tiles, so that every barrier is reached by all 256 threads.
+template <int KIND, int B, class RNew, class After>
+__device__ __forceinline__ void sweep_rows(int n, const double *__restrict__ pre, long lda, double *r, const SegView &zv,
+                                           double *rl, double &rr, double &rz, RNew r_new_of, After after)
+{
+    if constexpr (KIND == kPcBlock) {
+        for (int t = blockIdx.x; (long)t * 256 < n; t += gridDim.x) {   // (a tile counter: the loop's one induction variable)
+            const long i = (long)t * 256 + threadIdx.x;
+            const bool in = i < n;
+            const long wrow = in ? i : 0;
+            const BjEarly<B> e = bj_issue<B>(pre, lda, wrow);
+            const double rn = in ? r_new_of(i) : 0.0;
+            __syncthreads();   // the previous tile's chains have read rl
+            rl[threadIdx.x] = rn;
+            __syncthreads();
+            const double z = bj_chain<B>(e, pre, lda, wrow, rl);
+            if (in) {
+                const PcRow o = store_row<KIND>(rn, z, i, r, zv);
+                rr += o.rr;
+                rz += o.rz;
+                after(i);
+            }
+        }
+    } else {
+        for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {   // one trip up to 256 Ki rows
+            const double rn = r_new_of(i);
+            const PcRow o = store_row<KIND>(rn, KIND == kPcJacobi ? pre[i] : 0.0, i, r, zv);
+            rr += o.rr;
+            rz += o.rz;
+            after(i);
+        }
+    }
+}
+
+// K3 for vectors longer than 256 * kMaxVectorGrid rows (banded and CSR storage only: a dense matrix of that size does not
+// exist): the same arithmetic as update_xr_tile with the workgroups striding over the rows, so that the number of r.r
+// partials every K1 workgroup folds stays bounded.
+template <int KIND, int B>
+__device__ __forceinline__ void update_xr_strided(int n, int rows, int row0, const double *__restrict__ p_new, const SegView &apv,
+                                                  int tail_off, int tail_count, double *__restrict__ x, const SegView &rv,
+                                                  Scalars *sc, int parity, const double *__restrict__ pre, long lda,
+                                                  const SegView &zv, double *lds, double *rl)
+{
+    double *r = rv.base;
+    const int done = sc->done;
+    const double rsold = sc->rs[parity];
+    const double cs = fold_pap_strided(apv.base + apv.Sr + tail_off, apv.nranks, apv.S, tail_count);
+    if (done) return;
+    const double conj = block_sum<4>(cs, lds);
+    const double alpha = safeguarded_alpha(rsold, conj);
+    double rr = 0.0, rz = 0.0;
+    sweep_rows<KIND, B>(
+        n, pre, lda, r, zv, rl, rr, rz, [&](long i) { return fma(-alpha, seg_load(apv, (int)i), r[i]); },
+        [&](long i) {
+            const long li = i - row0;
+            if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);
+        });
+    store_partials<KIND>(rv, zv, rr, rz, lds);
+}
+
+// Set-up in front of the loop: r0 = b - A x0 (cg.cc:79-82; all rows: r is replicated), z0 by KIND, and the partials of
+// rsold = r.p with p == r (cg.cc:85,91) resp. of r.z and r.r, in K3's slots.
+template <int KIND, int B>
+__device__ __forceinline__ void init_residual_rows(int n, const double *__restrict__ b_full, const SegView &apv, const SegView &rv,
+                                                   const double *__restrict__ pre, long lda, const SegView &zv, double *lds,
+                                                   double *rl)
+{
+    double rr = 0.0, rz = 0.0;
+    sweep_rows<KIND, B>(
+        n, pre, lda, rv.base, zv, rl, rr, rz, [&](long i) { return b_full[i] - seg_load(apv, (int)i); }, [](long) {});
+    store_partials<KIND>(rv, zv, rr, rz, lds);
+}
+
+__global__ __launch_bounds__(256) void k_update_xr(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                    SegView apv, int tail_off, int tail_count,
+                                                    double *__restrict__ x, SegView rv, Scalars *sc, int parity,
+                                                    double *partials)
+{
+    __shared__ double lds[4];
+    update_xr_tile<kPcNone, 1>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, nullptr, 0, SegView{}, lds, nullptr);
+}
+
 __global__ __launch_bounds__(256) void k_update_xr_pc(int n, int rows, int row0, const double *__restrict__ p_new, SegView apv,
                                                        int tail_off, int tail_count, double *__restrict__ x, SegView rv, Scalars *sc,
                                                        int parity, const double *__restrict__ dinv, SegView zv)
 {
     __shared__ double lds[4];
-    double *r = rv.base;
-    const int done = sc->done;
-    const double rsold = sc->rs[parity];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int li = i - row0;
-    const bool in = i < n, own = in && li >= 0 && li < rows;
-    double ap_i = 0.0, r_i = 0.0, d_i = 0.0, p_i = 0.0, x_i = 0.0;
-    if (in) { ap_i = seg_load(apv, i); r_i = r[i]; d_i = dinv[i]; }
-    if (own) { p_i = p_new[i]; x_i = x[li]; }
-    double cs = 0.0;
-    {
-        const int total = apv.nranks * tail_count;
-        const double *tails = apv.base + apv.Sr + tail_off;
-        auto at = [&](int f) {
-            if (apv.nranks == 1) return tails[f];
-            const int q = f / tail_count;
-            return tails[(long)q * apv.S + (f - q * tail_count)];
-        };
-        for (int f = threadIdx.x; f < total; f += 4 * 256) {   // the plain kernel's order
-            double a[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int g = f + u * 256;
-                const double val = at(g < total ? g : total - 1);
-                a[u] = g < total ? val : 0.0;
-            }
-            cs += (a[0] + a[1]) + (a[2] + a[3]);
-        }
-    }
-    if (done) return;
-    const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);             // alpha = rho / p.Ap, the bound relative to rho
-    double rr = 0.0, rz = 0.0;
-    if (in) {
-        const PcRow o = pc_update_row(alpha, ap_i, r_i, d_i);
-        r[i] = o.r;
-        zv.base[i] = o.z;
-        rr = o.rr;
-        rz = o.rz;
-    }
-    if (own) x[li] = fma(alpha, p_i, x_i);
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
+    update_xr_tile<kPcJacobi, 1>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, dinv, 0, zv, lds, nullptr);
+}
+
+template <int B>
+__global__ __launch_bounds__(256) void k_update_xr_bj(int n, int rows, int row0, const double *__restrict__ p_new, SegView apv,
+                                                       int tail_off, int tail_count, double *__restrict__ x, SegView rv, Scalars *sc,
+                                                       int parity, const double *__restrict__ W, long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    update_xr_tile<kPcBlock, B>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, W, lda, zv, lds, rl);
+}
+
+__global__ __launch_bounds__(256) void k_update_xr_strided(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                            SegView apv, int tail_off, int tail_count,
+                                                            double *__restrict__ x, SegView rv, Scalars *sc, int parity)
+{
+    __shared__ double lds[4];
+    update_xr_strided<kPcNone, 1>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, nullptr, 0, SegView{}, lds, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_update_xr_strided_pc(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
+                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ dinv,
+                                                               SegView zv)
+{
+    __shared__ double lds[4];
+    update_xr_strided<kPcJacobi, 1>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, dinv, 0, zv, lds, nullptr);
+}
+
+template <int B>
+__global__ __launch_bounds__(256) void k_update_xr_strided_bj(int n, int rows, int row0, const double *__restrict__ p_new,
+                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
+                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ W,
+                                                               long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    update_xr_strided<kPcBlock, B>(n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc, parity, W, lda, zv, lds, rl);
+}
+
+__global__ __launch_bounds__(256) void k_init_residual(int n, const double *__restrict__ b_full, SegView apv,
+                                                        SegView rv, double *__restrict__ partials)
+{
+    __shared__ double lds[4];
+    init_residual_rows<kPcNone, 1>(n, b_full, apv, rv, nullptr, 0, SegView{}, lds, nullptr);
+}
+
+__global__ __launch_bounds__(256) void k_init_residual_pc(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
+                                                           const double *__restrict__ dinv, SegView zv)
+{
+    __shared__ double lds[4];
+    init_residual_rows<kPcJacobi, 1>(n, b_full, apv, rv, dinv, 0, zv, lds, nullptr);
+}
+
+template <int B>
+__global__ __launch_bounds__(256) void k_init_residual_bj(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
+                                                           const double *__restrict__ W, long lda, SegView zv)
+{
+    __shared__ double lds[4];
+    __shared__ double rl[256];
+    init_residual_rows<kPcBlock, B>(n, b_full, apv, rv, W, lda, zv, lds, rl);
 }
 
 // Loop ran out after k iterations: the tail of iteration k-1 that the next K1 would have done (same code,
@@ -589,40 +770,6 @@ __global__ __launch_bounds__(256) void k_reduce_partials(const double *__restric
 // ------------------------------------------------------------------------------------------------
 // setup / verification kernels (outside the iteration loop)
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_init_residual(int n, const double *__restrict__ b_full, SegView apv,
-                                                        SegView rv, double *__restrict__ partials)
-{
-    __shared__ double lds[4];
-    double *r = rv.base;
-    double rr = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {   // one trip up to 256 Ki rows
-        const double rvv = b_full[i] - seg_load(apv, (int)i);   // r = b - A x, cg.cc:79-82 (all rows: r is replicated)
-        r[i] = rvv;
-        rr += rvv * rvv;                                        // rsold = r.p with p == r, cg.cc:85,91
-    }
-    rr = block_sum<4>(rr, lds);
-    if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;   // same slots as K3's partials: K1(0) folds them (cg.cc:91-92)
-}
-
-// Jacobi set-up: r0 = b - A x0 as k_init_residual, z0 = dinv r0, the r.z / r.r partials into zv (k_update_xr_pc's slots).
-__global__ __launch_bounds__(256) void k_init_residual_pc(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
-                                                           const double *__restrict__ dinv, SegView zv)
-{
-    __shared__ double lds[4];
-    double *r = rv.base;
-    double rr = 0.0, rz = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const PcRow o = pc_row(b_full[i] - seg_load(apv, (int)i), dinv[i]);
-        r[i] = o.r;
-        zv.base[i] = o.z;
-        rr += o.rr;
-        rz += o.rz;
-    }
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
-}
-
 // Jacobi set-up, once per problem: the diagonal of the shard's rows into its Ap slice (then gathered like Ap) ...
 __global__ __launch_bounds__(256) void k_diag_slice(const double *__restrict__ A, long lda, int rows, int row0, double *__restrict__ dst)
 {
@@ -794,267 +941,7 @@ __global__ void k_loopback_gather(double *const *gathered_ptrs, const Scalars *c
     }
 }
 
-// K3 for vectors longer than 256 * kMaxVectorGrid rows (banded storage only: a dense matrix of that size does not
-// exist): the same arithmetic as k_update_xr with the workgroups striding over the rows, so that the number of r.r
-// partials every K1 workgroup folds stays bounded.
-__global__ __launch_bounds__(256) void k_update_xr_strided(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                            SegView apv, int tail_off, int tail_count,
-                                                            double *__restrict__ x, SegView rv, Scalars *sc, int parity)
-{
-    __shared__ double lds[4];
-    double *r = rv.base;
-    const int done = sc->done;
-    const double rsold = sc->rs[parity];
-    double cs = 0.0;
-    for (int q = 0; q < apv.nranks; ++q) {
-        const double *tail = apv.base + (long)q * apv.S + apv.Sr + tail_off;
-        for (int j = threadIdx.x; j < tail_count; j += 256) cs += tail[j];
-    }
-    if (done) return;
-    const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);             // cg.cc:107
-    double rr = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const double rn = fma(-alpha, seg_load(apv, (int)i), r[i]);   // cg.cc:113
-        r[i] = rn;
-        rr += rn * rn;                                                // cg.cc:116
-        const long li = i - row0;
-        if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);   // cg.cc:110
-    }
-    rr = block_sum<4>(rr, lds);
-    if (threadIdx.x == 0) r[rv.Sr + blockIdx.x] = rr;
-}
-
-// The Jacobi form of k_update_xr_strided (more than 256 * kMaxVectorGrid rows).
-__global__ __launch_bounds__(256) void k_update_xr_strided_pc(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
-                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ dinv,
-                                                               SegView zv)
-{
-    __shared__ double lds[4];
-    double *r = rv.base;
-    const int done = sc->done;
-    const double rsold = sc->rs[parity];
-    double cs = 0.0;
-    for (int q = 0; q < apv.nranks; ++q) {
-        const double *tail = apv.base + (long)q * apv.S + apv.Sr + tail_off;
-        for (int j = threadIdx.x; j < tail_count; j += 256) cs += tail[j];
-    }
-    if (done) return;
-    const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);
-    double rr = 0.0, rz = 0.0;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long)gridDim.x * 256) {
-        const PcRow o = pc_update_row(alpha, seg_load(apv, (int)i), r[i], dinv[i]);
-        r[i] = o.r;
-        zv.base[i] = o.z;
-        rr += o.rr;
-        rz += o.rz;
-        const long li = i - row0;
-        if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);
-    }
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
-}
-
-// ------------------------------------------------------------------------------------------------
-// Block Jacobi: z = D_b^-1 r with the B x B diagonal blocks of A inverted once per matrix.
-// W[t * lda + i] = (D_b^-1)(i, s(i) + t), s(i) = i - i mod B: replicated like dinv, zero outside the (truncated last) block and in
-// the pad rows.  A workgroup of an update kernel owns 256 consecutive global rows starting at a multiple of 256, and B divides
-// 256, so a tile holds whole blocks: its 256 values of r_new go to LDS and thread i runs ONE fma chain from +0.0 over t = 0 ...
-// B-1 ascending, acc = fma(W[t][i], r_new[s(i) + t], acc) -- the same chain in every kernel below, so z_i depends on (i, B)
-// only.  (Terms beyond a truncated block are fma(0, 0, acc) = acc.)
-// ------------------------------------------------------------------------------------------------
-constexpr int kBjEarly = 16;   // W loads issued ahead of the first wait (they do not depend on alpha); the rest in steps of 8
-
-template <int B>
-struct BjEarly {
-    static constexpr int N = B < kBjEarly ? B : kBjEarly;
-    double w[N];
-};
-
-// the thread's first W entries; `row` is clamped by the caller to a row that exists (a pad row's z is never stored)
-template <int B>
-__device__ __forceinline__ BjEarly<B> bj_issue(const double *__restrict__ W, long lda, long row)
-{
-    BjEarly<B> e;
-#pragma unroll
-    for (int t = 0; t < BjEarly<B>::N; ++t) e.w[t] = W[(long)t * lda + row];
-    return e;
-}
-
-// z_i from the tile's r_new in LDS (rl[0 .. 256), written and barriered by the caller)
-template <int B>
-__device__ __forceinline__ double bj_chain(const BjEarly<B> &e, const double *__restrict__ W, long lda, long row, const double *rl)
-{
-    const double *rb = rl + ((int)threadIdx.x & ~(B - 1));   // the block's start inside the tile: an LDS broadcast per quarter wave
-    double acc = 0.0;
-#pragma unroll
-    for (int t = 0; t < BjEarly<B>::N; ++t) acc = fma(e.w[t], rb[t], acc);
-    if constexpr (B > kBjEarly) {
-        const double *wp = W + (long)kBjEarly * lda + row;
-#pragma unroll 1   // one running pointer: unrolled, the B - 16 row offsets t * lda spill scalar registers
-        for (int t0 = kBjEarly; t0 < B; t0 += 8, wp += 8 * lda) {
-            double w[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) w[u] = wp[(long)u * lda];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) acc = fma(w[u], rb[t0 + u], acc);
-        }
-    }
-    return acc;
-}
-
-__device__ __forceinline__ PcRow bj_row(double r_new, double z)
-{
-    PcRow o;
-    o.r = r_new;
-    o.z = z;
-    o.rr = r_new * r_new;
-    o.rz = r_new * z;
-    return o;
-}
-
-// K3, block-Jacobi form of k_update_xr_pc: the same loads, the same alpha, the same partials; z from the chain above.
-template <int B>
-__global__ __launch_bounds__(256) void k_update_xr_bj(int n, int rows, int row0, const double *__restrict__ p_new, SegView apv,
-                                                       int tail_off, int tail_count, double *__restrict__ x, SegView rv, Scalars *sc,
-                                                       int parity, const double *__restrict__ W, long lda, SegView zv)
-{
-    __shared__ double lds[4];
-    __shared__ double rl[256];
-    double *r = rv.base;
-    const int done = sc->done;
-    const double rsold = sc->rs[parity];
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    const int li = i - row0;
-    const bool in = i < n, own = in && li >= 0 && li < rows;
-    double ap_i = 0.0, r_i = 0.0, p_i = 0.0, x_i = 0.0;
-    if (in) { ap_i = seg_load(apv, i); r_i = r[i]; }
-    if (own) { p_i = p_new[i]; x_i = x[li]; }
-    const long wrow = in ? i : 0;
-    const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
-    double cs = 0.0;
-    {
-        const int total = apv.nranks * tail_count;
-        const double *tails = apv.base + apv.Sr + tail_off;
-        auto at = [&](int f) {
-            if (apv.nranks == 1) return tails[f];
-            const int q = f / tail_count;
-            return tails[(long)q * apv.S + (f - q * tail_count)];
-        };
-        for (int f = threadIdx.x; f < total; f += 4 * 256) {   // the plain kernel's order
-            double a[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                const int g = f + u * 256;
-                const double val = at(g < total ? g : total - 1);
-                a[u] = g < total ? val : 0.0;
-            }
-            cs += (a[0] + a[1]) + (a[2] + a[3]);
-        }
-    }
-    if (done) return;
-    const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);
-    const double rn = in ? fma(-alpha, ap_i, r_i) : 0.0;   // rows past n: exactly 0, they meet W's zeros only
-    rl[threadIdx.x] = rn;
-    __syncthreads();
-    const double z = bj_chain<B>(e, W, lda, wrow, rl);
-    double rr = 0.0, rz = 0.0;
-    if (in) {
-        const PcRow o = bj_row(rn, z);
-        r[i] = o.r;
-        zv.base[i] = o.z;
-        rr = o.rr;
-        rz = o.rz;
-    }
-    if (own) x[li] = fma(alpha, p_i, x_i);
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
-}
-
-// The block form of k_update_xr_strided_pc (more than 256 * kMaxVectorGrid rows): the workgroups stride over whole tiles, so
-// that every barrier is reached by all 256 threads.
-template <int B>
-__global__ __launch_bounds__(256) void k_update_xr_strided_bj(int n, int rows, int row0, const double *__restrict__ p_new,
-                                                               SegView apv, int tail_off, int tail_count, double *__restrict__ x,
-                                                               SegView rv, Scalars *sc, int parity, const double *__restrict__ W,
-                                                               long lda, SegView zv)
-{
-    __shared__ double lds[4];
-    __shared__ double rl[256];
-    double *r = rv.base;
-    const int done = sc->done;
-    const double rsold = sc->rs[parity];
-    double cs = 0.0;
-    for (int q = 0; q < apv.nranks; ++q) {
-        const double *tail = apv.base + (long)q * apv.S + apv.Sr + tail_off;
-        for (int j = threadIdx.x; j < tail_count; j += 256) cs += tail[j];
-    }
-    if (done) return;
-    const double conj = block_sum<4>(cs, lds);
-    const double alpha = safeguarded_alpha(rsold, conj);
-    double rr = 0.0, rz = 0.0;
-    for (long base = (long)blockIdx.x * 256; base < n; base += (long)gridDim.x * 256) {
-        const long i = base + threadIdx.x;
-        const bool in = i < n;
-        const long wrow = in ? i : 0;
-        const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
-        const double rn = in ? fma(-alpha, seg_load(apv, (int)i), r[i]) : 0.0;
-        __syncthreads();   // the previous tile's chains have read rl
-        rl[threadIdx.x] = rn;
-        __syncthreads();
-        const double z = bj_chain<B>(e, W, lda, wrow, rl);
-        if (in) {
-            const PcRow o = bj_row(rn, z);
-            r[i] = o.r;
-            zv.base[i] = o.z;
-            rr += o.rr;
-            rz += o.rz;
-            const long li = i - row0;
-            if (li >= 0 && li < rows) x[li] = fma(alpha, p_new[i], x[li]);
-        }
-    }
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
-}
-
-// Block-Jacobi set-up: r0 = b - A x0 as k_init_residual_pc, z0 = D_b^-1 r0 by the same chain.
-template <int B>
-__global__ __launch_bounds__(256) void k_init_residual_bj(int n, const double *__restrict__ b_full, SegView apv, SegView rv,
-                                                           const double *__restrict__ W, long lda, SegView zv)
-{
-    __shared__ double lds[4];
-    __shared__ double rl[256];
-    double *r = rv.base;
-    double rr = 0.0, rz = 0.0;
-    for (long base = (long)blockIdx.x * 256; base < n; base += (long)gridDim.x * 256) {
-        const long i = base + threadIdx.x;
-        const bool in = i < n;
-        const long wrow = in ? i : 0;
-        const BjEarly<B> e = bj_issue<B>(W, lda, wrow);
-        const double rn = in ? b_full[i] - seg_load(apv, (int)i) : 0.0;
-        __syncthreads();
-        rl[threadIdx.x] = rn;
-        __syncthreads();
-        const double z = bj_chain<B>(e, W, lda, wrow, rl);
-        if (in) {
-            const PcRow o = bj_row(rn, z);
-            r[i] = o.r;
-            zv.base[i] = o.z;
-            rr += o.rr;
-            rz += o.rz;
-        }
-    }
-    rr = block_sum<4>(rr, lds);
-    rz = block_sum<4>(rz, lds);
-    if (threadIdx.x == 0) pc_store_partials(zv, blockIdx.x, rz, rr);
-}
-
+// Block Jacobi, set-up.
 // Set-up, extraction: dst[y * dst_stride + i] = A(row0 + i, s(row0 + i) + t) for t = t0 + y (y = blockIdx.y), 0 where that column
 // lies past n (the truncated last block).  One rank: dst = W, dst_stride = lda, all t in one launch; several: dst = the shard's Ap
 // slice, one t per launch, gathered like the diagonal.
@@ -1610,45 +1497,46 @@ int update_xr_grid(int count)
     return g < kMaxVectorGrid ? g : kMaxVectorGrid;
 }
 
+// f(std::integral_constant<int, B>) for the block size as a compile-time B; false: not an allowed size
+template <class F>
+static bool with_bj_block(int block, F f)
+{
+    switch (block) {
+    case 2: f(std::integral_constant<int, 2>{}); return true;
+    case 4: f(std::integral_constant<int, 4>{}); return true;
+    case 8: f(std::integral_constant<int, 8>{}); return true;
+    case 16: f(std::integral_constant<int, 16>{}); return true;
+    case 32: f(std::integral_constant<int, 32>{}); return true;
+    case 64: f(std::integral_constant<int, 64>{}); return true;
+    case 128: f(std::integral_constant<int, 128>{}); return true;
+    case 256: f(std::integral_constant<int, 256>{}); return true;
+    default: return false;
+    }
+}
+
 hipError_t launch_update_xr(int n, int rows, int row0, const double *p_new, SegView apv, int tail_off, int tail_count,
                             double *x, SegView rv, Scalars *sc, int parity, double *partials, hipStream_t s, hipEvent_t e0,
-                            hipEvent_t e1, const double *dinv, SegView zv, const double *W, int block, long lda)
+                            hipEvent_t e1, const UpdatePrecond &pc)
 {
-    if (W) {   // block Jacobi (block > 1): the k_update_xr_bj family
-        const bool tile = (long)update_xr_grid(n) * 256 >= n;
-        const dim3 grid(update_xr_grid(n));
-#define CGX_BJ_UPDATE(BB)                                                                                                          \
-    case BB:                                                                                                                       \
-        if (tile)                                                                                                                  \
-            hipExtLaunchKernelGGL((k_update_xr_bj<BB>), grid, dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, tail_off,     \
-                                  tail_count, x, rv, sc, parity, W, lda, zv);                                                     \
-        else                                                                                                                       \
-            hipExtLaunchKernelGGL((k_update_xr_strided_bj<BB>), grid, dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,       \
-                                  tail_off, tail_count, x, rv, sc, parity, W, lda, zv);                                           \
-        break;
-        switch (block) {
-            CGX_BJ_UPDATE(2) CGX_BJ_UPDATE(4) CGX_BJ_UPDATE(8) CGX_BJ_UPDATE(16) CGX_BJ_UPDATE(32) CGX_BJ_UPDATE(64)
-            CGX_BJ_UPDATE(128) CGX_BJ_UPDATE(256)
-        default: return hipErrorInvalidValue;
-        }
-#undef CGX_BJ_UPDATE
-        return hipGetLastError();
+    const dim3 grid(update_xr_grid(n));
+    const bool tile = (long)grid.x * 256 >= n;   // one row per thread: every dense problem
+    auto go = [&](auto kernel, auto... last) {
+        hipExtLaunchKernelGGL(kernel, grid, dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, tail_off, tail_count, x, rv, sc,
+                              parity, last...);
+    };
+    if (pc.kind == kPrecBlock) {
+        const bool ok = with_bj_block(pc.block, [&](auto B) {
+            if (tile) go(k_update_xr_bj<decltype(B)::value>, pc.W, pc.lda, pc.zv);
+            else go(k_update_xr_strided_bj<decltype(B)::value>, pc.W, pc.lda, pc.zv);
+        });
+        if (!ok) return hipErrorInvalidValue;
+    } else if (pc.kind == kPrecJacobi) {
+        if (tile) go(k_update_xr_pc, pc.dinv, pc.zv);
+        else go(k_update_xr_strided_pc, pc.dinv, pc.zv);
+    } else {
+        if (tile) go(k_update_xr, partials);
+        else go(k_update_xr_strided);
     }
-    if (dinv) {
-        if ((long)update_xr_grid(n) * 256 >= n)
-            hipExtLaunchKernelGGL(k_update_xr_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,
-                                  tail_off, tail_count, x, rv, sc, parity, dinv, zv);
-        else
-            hipExtLaunchKernelGGL(k_update_xr_strided_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new,
-                                  apv, tail_off, tail_count, x, rv, sc, parity, dinv, zv);
-        return hipGetLastError();
-    }
-    if ((long)update_xr_grid(n) * 256 >= n)   // one row per thread: every dense problem
-        hipExtLaunchKernelGGL(k_update_xr, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv, tail_off,
-                              tail_count, x, rv, sc, parity, partials);
-    else
-        hipExtLaunchKernelGGL(k_update_xr_strided, dim3(update_xr_grid(n)), dim3(256), 0, s, e0, e1, 0, n, rows, row0, p_new, apv,
-                              tail_off, tail_count, x, rv, sc, parity);
     return hipGetLastError();
 }
 
@@ -1856,23 +1744,19 @@ hipError_t launch_solve_end(int n, const double *Ax, const double *b, const doub
 }
 
 hipError_t launch_init_residual(int n, const double *b_full, SegView apv, SegView rv, double *partials, hipStream_t s,
-                                const double *dinv, SegView zv, const double *W, int block, long lda)
+                                const UpdatePrecond &pc)
 {
-    if (W) {
-#define CGX_BJ_INIT(BB)                                                                                                            \
-    case BB:                                                                                                                       \
-        hipLaunchKernelGGL((k_init_residual_bj<BB>), dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, W, lda, zv);    \
-        break;
-        switch (block) {
-            CGX_BJ_INIT(2) CGX_BJ_INIT(4) CGX_BJ_INIT(8) CGX_BJ_INIT(16) CGX_BJ_INIT(32) CGX_BJ_INIT(64) CGX_BJ_INIT(128)
-            CGX_BJ_INIT(256)
-        default: return hipErrorInvalidValue;
-        }
-#undef CGX_BJ_INIT
-        return hipGetLastError();
+    const dim3 grid(update_xr_grid(n));
+    if (pc.kind == kPrecBlock) {
+        const bool ok = with_bj_block(pc.block, [&](auto B) {
+            hipLaunchKernelGGL((k_init_residual_bj<decltype(B)::value>), grid, dim3(256), 0, s, n, b_full, apv, rv, pc.W, pc.lda, pc.zv);
+        });
+        if (!ok) return hipErrorInvalidValue;
+    } else if (pc.kind == kPrecJacobi) {
+        hipLaunchKernelGGL(k_init_residual_pc, grid, dim3(256), 0, s, n, b_full, apv, rv, pc.dinv, pc.zv);
+    } else {
+        hipLaunchKernelGGL(k_init_residual, grid, dim3(256), 0, s, n, b_full, apv, rv, partials);
     }
-    if (dinv) hipLaunchKernelGGL(k_init_residual_pc, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, dinv, zv);
-    else hipLaunchKernelGGL(k_init_residual, dim3(update_xr_grid(n)), dim3(256), 0, s, n, b_full, apv, rv, partials);
     return hipGetLastError();
 }
 

@@ -261,20 +261,7 @@ __global__ __launch_bounds__(256) void k_lr_update(int n, const double *__restri
             p_i = p_new[i];
             x_i = x[i];
         }
-        double cs = 0.0;
-        {
-            const double *tails = apv.base + apv.Sr;
-            for (int f = tid; f < tail_count; f += 4 * 256) {   // the plain kernel's order
-                double a[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int g = f + u * 256;
-                    const double val = tails[g < tail_count ? g : tail_count - 1];
-                    a[u] = g < tail_count ? val : 0.0;
-                }
-                cs += (a[0] + a[1]) + (a[2] + a[3]);
-            }
-        }
+        const double cs = fold_pap(apv.base + apv.Sr, 1, 0, tail_count);
         if (done) return;   // converged earlier (uniform over the grid): nothing is written
         const double conj = block_sum<4>(cs, lds);
         const double alpha = safeguarded_alpha(rsold, conj);   // alpha = rho / p.Ap

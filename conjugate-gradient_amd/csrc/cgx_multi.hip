@@ -246,19 +246,8 @@ __global__ __launch_bounds__(256) void k_multi_update(int n, long lda, const dou
     const bool in = i < n;
     double ap_i = 0.0, r_i = 0.0, p_i = 0.0, x_i = 0.0;
     if (in) { ap_i = Y[off]; r_i = r[off]; p_i = p[off]; x_i = x[off]; }
-    const double *part = partials + (long)j * g1;
-    double cs = 0.0;
-    for (int f = threadIdx.x; f < g1; f += 4 * 256) {
-        double a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int g = f + u * 256;
-            const double val = part[g < g1 ? g : g1 - 1];
-            a[u] = g < g1 ? val : 0.0;
-        }
-        cs += (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    if (done) return;                                       // frozen column (uniform over the workgroup)
+    const double cs = fold_pap(partials + (long)j * g1, 1, 0, g1);
+    if (done) return;                                      // frozen column (uniform over the workgroup)
     const double conj = block_sum<4>(cs, lds);
     const double alpha = safeguarded_alpha(rsold, conj);
     double rr = 0.0;

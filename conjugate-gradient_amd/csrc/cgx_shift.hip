@@ -30,28 +30,6 @@ namespace {
 
 constexpr double kZetaFloor = 0x1.0p-500;
 
-// alpha_k as K3 computes it (k_update_xr: one flat index over the partials, four loads in flight, block_sum; k_update_xr_strided:
-// a lane-strided sum, block_sum).  All 256 threads of the workgroup.
-__device__ __forceinline__ double fold_pap(const double *__restrict__ pap, int total, bool strided)
-{
-    double cs = 0.0;
-    if (strided) {
-        for (int j = threadIdx.x; j < total; j += 256) cs += pap[j];
-        return cs;
-    }
-    for (int f = threadIdx.x; f < total; f += 4 * 256) {
-        double a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int g = f + u * 256;
-            const double val = pap[g < total ? g : total - 1];
-            a[u] = g < total ? val : 0.0;
-        }
-        cs += (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    return cs;
-}
-
 // The loads of head_issue for the r.r partials, and head_finish's fold of them (every wave on its own, no LDS).
 struct RrLoads {
     double a[4];
@@ -114,7 +92,8 @@ __global__ __launch_bounds__(256) void k_shift_update(ShiftArgs a)
         pv[j] = a.P[off];
     }
     const RrLoads rl = rr_issue(a.rrp, a.nrr);
-    const double cs = fold_pap(a.pap, a.npap, a.pap_strided != 0);   // (a loop with its own waits: behind every other load)
+    // alpha_k as K3 computes it, in the order of k_update_xr or k_update_xr_strided (a loop with its own waits: behind every other load)
+    const double cs = a.pap_strided ? fold_pap_strided(a.pap, 1, 0, a.npap) : fold_pap(a.pap, 1, 0, a.npap);
     if (all_at < k) return;                                        // the loop has ended (uniform over the grid): nothing is written
 
     const double conj = block_sum<4>(cs, lds);

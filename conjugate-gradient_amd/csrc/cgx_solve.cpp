@@ -247,12 +247,26 @@ cgx_status harvest_gemv_events(cgx_ctx *ctx)
     return CGX_OK;
 }
 
+// How K3 and the residual set-up of shard s make z: Jacobi from dinv, block Jacobi (block > 1) from W -- the update kernel's
+// block form, never with the exchange inside; any other preconditioner: not at all.
+static cgx::UpdatePrecond update_precond(const cgx_ctx *ctx, const Shard &s)
+{
+    cgx::UpdatePrecond pc;
+    if (ctx->precond != CGX_PRECOND_JACOBI) return pc;
+    pc.kind = ctx->precond_block > 1 ? cgx::kPrecBlock : cgx::kPrecJacobi;
+    pc.dinv = s.dinv;
+    pc.W = s.W;
+    pc.block = ctx->precond_block;
+    pc.lda = ctx->lda;
+    pc.zv = s.zv;
+    return pc;
+}
+
 // ---- one body of the loop cg.cc:96-137: two kernels, one exchange ------------------------------------
 cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
 {
     hipStream_t st = ctx->stream;
     const bool pc = ctx->precond == CGX_PRECOND_JACOBI;
-    const bool bj = pc && ctx->precond_block > 1;   // block Jacobi: the update kernel's block form (never with the exchange inside)
     // tail of iteration k-1 (cg.cc:117-132) + GEMV and p.Ap partials of iteration k (cg.cc:100-105)
     for (auto &s : ctx->shards) CGX_TRY(run_gemv_fused(ctx, s, k));
     if (ctx->precond == CGX_PRECOND_PIVCHOL) {
@@ -295,7 +309,7 @@ cgx_status enqueue_iteration(cgx_ctx *ctx, int k)
         const int count = folded ? 1 : (s.plan.variant == 6 ? cgx::plan_partials(s.plan) : ctx->npart);
         HIP_TRY(ctx, cgx::launch_update_xr(ctx->n, s.rows, s.row0, s.p[(k + 1) & 1], s.apv, folded ? ctx->npart : 0,
                                            count, s.x, s.rv, s.sc, k & 1, s.partials, st, u0, u1,   // cg.cc:105-116
-                                           pc ? s.dinv : nullptr, s.zv, bj ? s.W : nullptr, ctx->precond_block, ctx->lda));
+                                           update_precond(ctx, s)));
     }
     return CGX_OK;
 }
@@ -670,8 +684,7 @@ cgx_status cgx_solve_begin(cgx_ctx *ctx, const double *x0)
     CGX_TRY(gather_segments(ctx, false));
     for (auto &s : ctx->shards)
         HIP_TRY(ctx, cgx::launch_init_residual(n, s.b_full, s.apv, s.rv, s.partials, st,            // cg.cc:82 (Jacobi: and z0)
-                                               pc ? s.dinv : nullptr, s.zv, pc && ctx->precond_block > 1 ? s.W : nullptr,
-                                               ctx->precond_block, ctx->lda));
+                                               update_precond(ctx, s)));
     if (lr) {   // z0 = P^-1 r0 behind the plain initial residual: the partials of L^T r0 and of r0.r0, then the apply kernel
         Shard &s = ctx->shards[0];
         const cgx::LrWork w = lr_work(ctx);

@@ -81,3 +81,19 @@ def test_new_kernels_never_spill(new_kernels):
     # what 256 threads x 4 workgroups per CU allow): none of them needs more
     for b in BLOCKS:
         assert int(new_kernels["cgx::k_update_xr_bj<%d>" % b]["VGPRs"]) <= 128
+
+
+# VGPRs per block size (BLOCKS order) when every block form was a kernel text of its own; since they share their bodies with
+# the plain and Jacobi forms (update_xr_tile, update_xr_strided, init_residual_rows in cgx_kernels.hip) these are upper bounds
+BJ_VGPRS = {
+    "cgx::k_update_xr_bj": (34, 38, 52, 70, 70, 70, 70, 70),
+    "cgx::k_update_xr_strided_bj": (36, 42, 56, 74, 68, 68, 68, 66),
+    "cgx::k_init_residual_bj": (28, 34, 48, 68, 64, 64, 64, 62),
+}
+
+
+def test_block_forms_stay_within_their_vgprs(new_kernels):
+    for kernel, bounds in BJ_VGPRS.items():
+        for b, vgprs in zip(BLOCKS, bounds):
+            r = new_kernels["%s<%d>" % (kernel, b)]
+            assert int(r["VGPRs"]) <= vgprs, (kernel, b, r)

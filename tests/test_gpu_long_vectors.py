@@ -21,7 +21,7 @@ c. test_block_jacobi_exact_on_a_block_diagonal_matrix     every block of W is re
                                              second-trip tile alone leaves a residual
 d. test_block_inverses_of_the_second_trip    W itself for every row from 262144 on (k_csr_bj_col_slice's second trip,
                                              k_bj_invert on the blocks past 262144 and on the truncated one)
-e. test_zero_shift_is_the_plain_solve        fold_pap(strided = true) against k_update_xr_strided, rr_finish's loop over the
+e. test_zero_shift_is_the_plain_solve        fold_pap_strided in k_shift_update against k_update_xr_strided, rr_finish's loop over the
                                              partials from 256 on against head_finish's, pap_strided set by the host
 f. test_every_shift_against_longdouble       k_shift_update<8>'s second loop (it reads P and X again), k_shift_norms and the
                                              |zeta| sqrt(r.r) stores: every reported number against a value computed outside

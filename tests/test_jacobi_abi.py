@@ -147,6 +147,16 @@ def test_pcg_form_of_the_default_shape_keeps_four_workgroups_per_cu(kernel_rows)
     assert int(r["VGPRs"]) <= 128, r
 
 
+# VGPRs of the Jacobi forms of K3 and of the residual set-up when each was a kernel text of its own; since they share their
+# bodies with the plain and block forms (update_xr_tile, update_xr_strided, init_residual_rows) these are upper bounds
+PC_VGPRS = {"cgx::k_update_xr_pc": 32, "cgx::k_update_xr_strided_pc": 30, "cgx::k_init_residual_pc": 22}
+
+
+def test_jacobi_update_kernels_stay_within_their_vgprs(kernel_rows):
+    for name, vgprs in PC_VGPRS.items():
+        assert int(kernel_rows[name]["VGPRs"]) <= vgprs, (name, kernel_rows[name])
+
+
 def test_plain_instantiations_keep_their_figures(kernel_rows):
     for name, (vgpr, sgpr, lds, scratch) in PLAIN.items():
         assert name in kernel_rows, name
