@@ -327,7 +327,7 @@ cgx_status setup_problem(cgx_ctx *ctx, int n)
     ctx->chunked = (ctx->nranks > 1 && !ctx->sparse()) || fused_p2p;
     const bool allow_split = ctx->chunked && !ctx->sparse() && ctx->nranks > 1;
     // (40000 = the LDS-resident solver, setup_resident below: set-up, verification and the probes still run the default K1)
-    const int k1_variant = (variant == 40000 || variant == 50000) ? 0 : variant;
+    const int k1_variant = (variant == 40000 || variant == 50000 || variant == 60000) ? 0 : variant;
     auto plan_for = [&](int rows) {
         if (ctx->csr) return cgx::plan_csr(rows, 0, k1_variant);   // grid by rows only; L follows the matrix (plan_csr_shards)
         return ctx->banded ? cgx::plan_dia(rows, k1_variant) : cgx::plan_gemv(k1_variant, rows, ctx->n, ctx->lda, allow_split);
@@ -477,10 +477,15 @@ cgx_status plan_symmetric(cgx_ctx *ctx)
         if (e) variant = atoi(e);
     }
     // the general K1 exactly as setup_problem plans it for this shard (an explicit shape, 10821 say, stays what it asks for)
-    const int k1_variant = (variant == 40000 || variant == 50000) ? 0 : variant;
+    const int k1_variant = (variant == 40000 || variant == 50000 || variant == 60000) ? 0 : variant;
     const cgx::GemvPlan general = cgx::plan_gemv(k1_variant, s.rows, ctx->n, ctx->lda, false);
-    const cgx::GemvPlan sym = cgx::plan_symv(ctx->n, ctx->lda, ctx->cus);
-    const bool eligible = variant <= 0 && ctx->n > cgx::kSymvMinN && s.rows == ctx->n && s.A && sym.light <= ctx->npart;
+    // tiles per workgroup of the symmetric tile kernel: 60000 = the grid of 4 workgroups per CU; CGX_SYMV_RUN=0|1|2|4 in the
+    // environment moves the default (the measurements of profiles/symv_walk/)
+    int run = cgx::kSymvRun;
+    if (variant == 60000) run = 0;
+    else if (const char *e = getenv("CGX_SYMV_RUN")) run = std::min(std::max(atoi(e), 0), 64);
+    const cgx::GemvPlan sym = cgx::plan_symv(ctx->n, ctx->lda, ctx->cus, run);
+    const bool eligible = (variant <= 0 || variant == 60000) && ctx->n > cgx::kSymvMinN && s.rows == ctx->n && s.A && sym.light <= ctx->npart;
     if (!eligible) {
         s.plan = general;
         return CGX_OK;

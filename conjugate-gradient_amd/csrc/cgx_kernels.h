@@ -93,7 +93,11 @@ hipError_t launch_gemv_fused(const GemvPlan &plan, const double *A, long lda, in
 // the tile kernel, ncols as for variant 1.
 constexpr int kSymvTile = 256;
 constexpr int kSymvMinN = 16384;   // the default plan takes variant 6 only above this n
-GemvPlan plan_symv(int n, long lda, int cus);
+// run = tiles per workgroup of the static split: grid = tiles / run (runs of the grid differ by one tile at most); run = 0: the
+// grid of 4 workgroups per CU (gemv_variant 60000).  The tile kernel takes its run from gridDim.x: the same kernel, the same
+// bits, whatever the grid.
+constexpr int kSymvRun = 1;
+GemvPlan plan_symv(int n, long lda, int cus, int run = kSymvRun);
 // p.Ap partials a plan's launch leaves in the tail (variant 6: one per fold workgroup; otherwise one per K1 workgroup)
 inline int plan_partials(const GemvPlan &pl) { return pl.variant == 6 ? pl.light : pl.grid / (pl.split > 1 ? pl.split : 1); }
 // Plain form: Ap = A v (rows < n), partials[wg] = the fold workgroup's part of v . Ap.

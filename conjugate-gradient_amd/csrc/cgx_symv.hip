@@ -146,7 +146,7 @@ __global__ __launch_bounds__(256) void k_symmetric_check(const double *__restric
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
-GemvPlan plan_symv(int n, long lda, int cus)
+GemvPlan plan_symv(int n, long lda, int cus, int run)
 {
     GemvPlan pl{};
     pl.variant = 6;
@@ -155,7 +155,11 @@ GemvPlan plan_symv(int n, long lda, int cus)
     pl.nt = 1;
     pl.split = (n + kSymvTile - 1) / kSymvTile;                      // nb: blocks = slots per block
     const long tiles = (long)pl.split * (pl.split + 1) / 2;
-    const long slots = 4L * (cus > 0 ? cus : 256);                   // 4 workgroups per CU (128 VGPRs, 20 KiB of LDS each)
+    // run = 0: 4 workgroups per CU (128 VGPRs, 20 KiB of LDS each), what is resident at once; run > 0: tiles / run workgroups,
+    // which the dispatcher hands to the CUs as they come free ("variant 6")
+    long slots = run > 0 ? tiles / run : 4L * (cus > 0 ? cus : 256);
+    if (slots < 1) slots = 1;
+    if (slots > (1L << 30)) slots = 1L << 30;
     pl.grid = (int)(tiles < slots ? tiles : slots);
     pl.U = (int)((tiles + pl.grid - 1) / pl.grid);                   // tiles of the longest run
     const int Sr = (n + 1) / 2 * 2;

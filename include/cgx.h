@@ -102,6 +102,10 @@ typedef struct cgx_config {
                                  40000 = ask for the persistent kernel: CGX_ERR_UNSUPPORTED where it cannot be had, and an
                                  expired wait is CGX_ERR_HIP (no fallback; the context stays usable for the next problem);
                                  50000 = the same, but the STREAMING persistent kernel whatever the size (1024 <= n <= 16384);
+                                 60000 = the per-launch path with its default shape (as -1), but a symmetric A on one GPU
+                                 (plan variant 6, n > 16384) walks its tiles on the grid of 4 workgroups per CU instead of one
+                                 tile per workgroup: the same kernel and the same bits, kept as the A/B switch for the walk
+                                 ("variant 6"); a general A runs the default K1 shape;
                                  -1 = the per-launch path with its default shape, also where a persistent kernel would fit
                                  (as does CGX_RESIDENT=0 in the environment; CGX_STREAM_MAX=n moves the upper end of the
                                  default, 4096 = never stream); v*10000 + R*100 + U*10 + d = an explicit per-launch K1 shape,
