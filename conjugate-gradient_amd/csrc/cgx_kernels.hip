@@ -1052,36 +1052,45 @@ __global__ __launch_bounds__(256) void k_spmv_dia(DiaView dv, int rows, int row0
     // Two consecutive rows per thread, so that the diagonals (streamed once: non-temporal), the vectors, Ap and p_new
     // all move as 16-B pieces.  Row i+1 needs no guard: behind the last row the diagonals hold zeros (ld is even and
     // zero filled), the vectors are zero padded up to lda, and the Ap slice is padded to an even count.
+    // Where the pitch has no pad (lda == n) element n of a vector does not exist: a pair that would end on it is loaded one
+    // element lower (still one unconditional 16-B load) and its upper half stands for the 0 a pad would hold.
     // CH diagonals are in flight at a time: all their loads are issued before the first FMA (see K1 above).
     double d = 0.0;
     for (long i = ((long)blockIdx.x * 256 + threadIdx.x) * 2; i < rows; i += (long)gridDim.x * 512) {
         const int g = row0_global + (int)i;
-        const d2u pv = *reinterpret_cast<const d2u *>(v + g);
+        const bool gtop = (long)g + 1 >= lda;                             // row g is the vectors' last element
+        d2u pv = *reinterpret_cast<const d2u *>(v + (gtop ? g - 1 : g));
         d2u pr{0.0, 0.0};
-        if constexpr (FUSED) pr = *reinterpret_cast<const d2u *>(rfull + g);
+        if constexpr (FUSED) pr = *reinterpret_cast<const d2u *>(rfull + (gtop ? g - 1 : g));
+        if (gtop) {
+            pv = d2u{pv.y, 0.0};
+            pr = d2u{pr.y, 0.0};
+        }
         double acc0 = 0.0, acc1 = 0.0;
         for (int t0 = 0; t0 < dv.ndiag; t0 += CH) {
             d2u qv[CH], qr[CH];
             d2 a[CH];
-            bool low[CH];
+            bool low[CH], top[CH];
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 const int t = t0 + u < dv.ndiag ? t0 + u : dv.ndiag - 1;   // tail of the last chunk: re-load, not used
                 const int j = g + dv.off[t];                              // column of row g; row g+1 has j+1
                 const int jb = j < 0 ? 0 : (j > n - 1 ? n - 1 : j);       // outside [0,n): the stored value is 0
                 low[u] = j < 0;                                           // j == -1: row g+1 needs column 0 = pair.x
-                qv[u] = *reinterpret_cast<const d2u *>(v + jb);
-                if constexpr (FUSED) qr[u] = *reinterpret_cast<const d2u *>(rfull + jb);
+                top[u] = (long)jb + 1 >= lda;                             // jb == n - 1 == lda - 1: the pair one lower
+                const int jl = top[u] ? jb - 1 : jb;
+                qv[u] = *reinterpret_cast<const d2u *>(v + jl);
+                if constexpr (FUSED) qr[u] = *reinterpret_cast<const d2u *>(rfull + jl);
                 a[u] = load_a<true>(dv.vals + t * dv.ld + i);            // ld and i are even: 16-B aligned
             }
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int u = 0; u < CH; ++u) {
                 if (t0 + u < dv.ndiag) {
-                    double q0 = qv[u].x, q1 = low[u] ? qv[u].x : qv[u].y;
+                    double q0 = top[u] ? qv[u].y : qv[u].x, q1 = top[u] ? 0.0 : (low[u] ? qv[u].x : qv[u].y);
                     if constexpr (FUSED) {
-                        q0 = fma(beta, q0, qr[u].x);                      // same bits as the stored p_new[j]
-                        q1 = fma(beta, q1, low[u] ? qr[u].x : qr[u].y);
+                        q0 = fma(beta, q0, top[u] ? qr[u].y : qr[u].x);   // same bits as the stored p_new[j]
+                        q1 = fma(beta, q1, top[u] ? 0.0 : (low[u] ? qr[u].x : qr[u].y));
                     }
                     acc0 = fma(a[u].x, q0, acc0);                         // cg.cc:100-102
                     acc1 = fma(a[u].y, q1, acc1);
@@ -1092,7 +1101,8 @@ __global__ __launch_bounds__(256) void k_spmv_dia(DiaView dv, int rows, int row0
         if constexpr (FUSED) {
             p0 = fma(beta, p0, pr.x);
             p1 = fma(beta, p1, pr.y);
-            *reinterpret_cast<d2u *>(p_new + g) = d2u{p0, p1};            // column g+1 beyond the block: same value as
+            if (gtop) p_new[g] = p0;
+            else *reinterpret_cast<d2u *>(p_new + g) = d2u{p0, p1};       // column g+1 beyond the block: same value as
         }                                                                 // the pre-pass stores (r is replicated)
         d2 out;
         out.x = acc0;
@@ -1166,9 +1176,14 @@ __global__ __launch_bounds__(256) void k_spmv_dia_lds(DiaView dv, DiaWindows dw,
             const int t = u < dv.ndiag ? u : dv.ndiag - 1;
             a[u] = load_a<true>(dv.vals + t * dv.ld + il);
         }
-        const d2u pv = *reinterpret_cast<const d2u *>(v + g);
+        const bool gtop = (long)g + 1 >= lda;            // no pad and row g the vectors' last element: as in the direct form
+        d2u pv = *reinterpret_cast<const d2u *>(v + (gtop ? g - 1 : g));
         d2u pr{0.0, 0.0};
-        if constexpr (FUSED) pr = *reinterpret_cast<const d2u *>(rfull + g);
+        if constexpr (FUSED) pr = *reinterpret_cast<const d2u *>(rfull + (gtop ? g - 1 : g));
+        if (gtop) {
+            pv = d2u{pv.y, 0.0};
+            pr = d2u{pr.y, 0.0};
+        }
         // stage the windows: aligned pairs of columns, clamped at the ends of the vectors
         for (int w = 0; w < dw.nwin; ++w) {
             const int c0 = g0 + dw.start[w];              // even
@@ -1223,7 +1238,8 @@ __global__ __launch_bounds__(256) void k_spmv_dia_lds(DiaView dv, DiaWindows dw,
             if constexpr (FUSED) {
                 p0 = fma(beta, p0, pr.x);
                 p1 = fma(beta, p1, pr.y);
-                *reinterpret_cast<d2u *>(p_new + g) = d2u{p0, p1};
+                if (gtop) p_new[g] = p0;
+                else *reinterpret_cast<d2u *>(p_new + g) = d2u{p0, p1};
             }
             d2 out;
             out.x = acc0;

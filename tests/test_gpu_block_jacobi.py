@@ -115,13 +115,18 @@ def _begin(c, b):
                          + [("hash600", b) for b in (8, 128, 256)])
 def test_inverse_alone(gpu_pkg, name, block, storage):
     A, b = _matrix(name)
-    n = len(b)
     with _solver(gpu_pkg, storage) as c:
         _load(c, storage, A)
         c.set_preconditioner("jacobi", block=block)
         assert c.preconditioner_block() == block
         _begin(c, b)
         W = c._probe_precond_blocks()
+    _check_inverse(W, A, block, (name, storage))
+
+
+def _check_inverse(W, A, block, what):
+    """The block inverses as cgx_probe_get_precond_blocks returns them, against the diagonal blocks of A (item 1 of the header)."""
+    n = A.shape[0]
     assert W.shape == (n, block)
     worst = 0.0
     for s, e in ref.block_ranges(n, block):
@@ -134,7 +139,7 @@ def test_inverse_alone(gpu_pkg, name, block, storage):
         bar = 4 * m * EPS * float(np.linalg.cond(D, 2))
         worst = max(worst, err / bar)
         assert err <= bar, (s, m, err, bar)
-    print("inverse %s block %d %s: worst max|W D - I| / (4 m eps kappa) = %.3f" % (name, block, storage, worst))
+    print("inverse %r block %d: worst max|W D - I| / (4 m eps kappa) = %.3f" % (what, block, worst))
 
 
 # ---- 2. fixed iterations against the longdouble PCG --------------------------------------------------------------------------

@@ -159,24 +159,32 @@ def test_lane1_equals_banded_direct_form(gpu_pkg, n, p):
     assert np.array_equal(out[0][0], out[1][0])
 
 
-@pytest.mark.parametrize("L", LANES)
-@pytest.mark.parametrize("p", [1, 3])
-def test_every_lane_count_against_longdouble(gpu_pkg, L, p):
-    n = 3000
+def lanes_problem(n, L):
+    """(A, v, A v in longdouble): 2 % filled rows, every 97th row 60 % filled, one empty row, a dominant diagonal."""
     rng = np.random.default_rng(L)
     A = np.where(rng.random((n, n)) < 0.02, rng.standard_normal((n, n)), 0.0)
     A[::97, :] = np.where(rng.random((len(A[::97]), n)) < 0.6, rng.standard_normal((len(A[::97]), n)), 0.0)   # long rows
     A[50, :] = 0.0                                                                                              # an empty row
     A += np.diag(np.where(np.arange(n) == 50, 0.0, 100.0))   # p.Ap dominated by positive terms: a relative bound is meaningful
     v = rng.standard_normal(n)
-    yo = A.astype(np.longdouble) @ v.astype(np.longdouble)
+    return A, v, A.astype(np.longdouble) @ v.astype(np.longdouble)
+
+
+def check_lanes_product(A, v, yo, y, pap):
+    bound = 2e-14 * (np.abs(A) @ np.abs(v))
+    assert np.all(np.abs(y - yo.astype(np.float64)) <= bound + 1e-300)
+    assert rel(pap, float(v.astype(np.longdouble) @ yo)) < 1e-13
+
+
+@pytest.mark.parametrize("L", LANES)
+@pytest.mark.parametrize("p", [1, 3])
+def test_every_lane_count_against_longdouble(gpu_pkg, L, p):
+    A, v, yo = lanes_problem(3000, L)
     with solver(gpu_pkg, p, gemv_variant=70000 + L) as s:
         s.set_matrix_csr(*dense_to_csr(A))
         assert s.gemv_plan()["R"] == L
         y, pap = s.probe_gemv(v)
-    bound = 2e-14 * (np.abs(A) @ np.abs(v))
-    assert np.all(np.abs(y - yo.astype(np.float64)) <= bound + 1e-300)
-    assert rel(pap, float(v.astype(np.longdouble) @ yo)) < 1e-13
+    check_lanes_product(A, v, yo, y, pap)
 
 
 def test_row_result_depends_on_lanes_only(gpu_pkg):

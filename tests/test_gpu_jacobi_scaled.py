@@ -140,6 +140,7 @@ def _dense_pair(pkg, L, s, bt, iters, check_plan, what, **kw):
     _assert_same_bits(s, xj, xt, what)
     ax, aax = _dense_products(A, xj)
     _check_rel_residual(rj, ax, aax, s * bt, _row_entries(A), what)
+    return xt, xj, rj
 
 
 # ---- 1a. dense, one GPU, the per-launch K1 shapes ---------------------------------------------------------------------------
@@ -243,8 +244,8 @@ def _csr_check(p, L=0):
     return check
 
 
-def _csr_run(pkg, p, L, csr, b, iters, jacobi):
-    with tc.solver(pkg, p, gemv_variant=L) as c:
+def _csr_run(pkg, p, L, csr, b, iters, jacobi, **kw):
+    with tc.solver(pkg, p, gemv_variant=L, **kw) as c:
         c.set_matrix_csr(*csr)
         _csr_check(p, L)(c)
         assert c.matrix_nnz(0) > 0 and sum(c.matrix_nnz(q) for q in range(p)) == len(csr[2])

@@ -151,11 +151,16 @@ def test_gemv_linearity(gpu_pkg):
 # ---- K3 / K4 -----------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n", [1, 255, 256, 257, 1000, 4096, 32768, 100003])
 def test_vector_ops(gpu_pkg, oracle, n):
+    with gpu_pkg.CGSolver() as s:
+        vector_ops_case(s, oracle, n)
+
+
+def vector_ops_case(s, oracle, n):
+    """probe_vector_ops on context s for seeded vectors of length n, checked; returns what the probe returned."""
     rng = np.random.default_rng(n)
     x, r, p, Ap = (rng.standard_normal(n) for _ in range(4))
     alpha, beta = 0.37, 1.9
-    with gpu_pkg.CGSolver() as s:
-        x2, r2, p2, rr = s.probe_vector_ops(alpha, beta, x, r, p, Ap)
+    x2, r2, p2, rr = s.probe_vector_ops(alpha, beta, x, r, p, Ap)
     xe = x + alpha * p                    # cblas_daxpy, cg.cc:110
     re_ = r - alpha * Ap                  # cg.cc:113
     pe = re_ + beta * p                   # cg.cc:127-129
@@ -163,6 +168,7 @@ def test_vector_ops(gpu_pkg, oracle, n):
     assert np.allclose(r2, re_, rtol=0, atol=4e-16 * (np.abs(r) + np.abs(alpha * Ap)).max())
     assert np.allclose(p2, pe, rtol=0, atol=8e-16 * (np.abs(re_) + np.abs(beta * p)).max())
     assert rel(rr, oracle.dot(re_, re_)) < 1e-13
+    return x2, r2, p2, rr
 
 
 # ---- init_source_term, the safeguard of alpha -----------------------------------------------------------------------

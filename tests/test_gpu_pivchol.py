@@ -41,11 +41,14 @@ def _vectors(n):
     return {"b": np.array(b), "e_7": e7, "random": np.random.default_rng(7).standard_normal(n)}
 
 
-def _device_factor(gpu_pkg, n, rank):
-    """What the device made for (n, rank), once per session: pivots, L, delta, P^-1 of three vectors, delta with shift 0.25."""
-    key = (n, rank)
+def _device_factor(gpu_pkg, n, rank, check=None, **kw):
+    """What the device made for (n, rank), once per session: pivots, L, delta, P^-1 of three vectors, delta with shift 0.25.
+    kw: further settings of the context (a row pitch, say), part of the key; check(s): asserted on the context first."""
+    key = (n, rank) + tuple(sorted(kw.items()))
     if key not in _CACHE:
-        with _solver(gpu_pkg, n) as s:
+        with _solver(gpu_pkg, n, **kw) as s:
+            if check is not None:
+                check(s)
             s.set_preconditioner("pivchol", rank=rank)
             assert s.preconditioner == "pivchol" and s.preconditioner_rank() == rank
             assert s.preconditioner_shift() == (0.0, 0.0)          # nothing made yet
@@ -65,8 +68,11 @@ def _device_factor(gpu_pkg, n, rank):
 # ---- 1. the factor -------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,rank", SHAPES)
 def test_factor(gpu_pkg, n, rank):
+    _check_factor(_device_factor(gpu_pkg, n, rank), n, rank)
+
+
+def _check_factor(f, n, rank):
     A, _ = _problem(n)
-    f = _device_factor(gpu_pkg, n, rank)
     piv, L, delta = f["piv"], f["L"], f["delta"]
     assert len(set(piv.tolist())) == rank and piv.min() >= 0 and piv.max() < n
     ratio, mean_ld = ref.remaining_diagonal_checks(A, piv, L)
@@ -85,7 +91,10 @@ def test_factor(gpu_pkg, n, rank):
 # ---- 2. the apply --------------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,rank", SHAPES)
 def test_apply(gpu_pkg, n, rank):
-    f = _device_factor(gpu_pkg, n, rank)
+    _check_apply(_device_factor(gpu_pkg, n, rank), n, rank)
+
+
+def _check_apply(f, n, rank):
     w64 = ref.Woodbury(f["L"], f["delta"], np.float64)
     wld = ref.Woodbury(f["L"], f["delta"], ref.LD)
     for name, v in _vectors(n).items():
