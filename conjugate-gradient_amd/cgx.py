@@ -39,6 +39,7 @@ EXPORTS = [
     "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
     "cgx_set_preconditioner_rank", "cgx_get_preconditioner_rank", "cgx_set_preconditioner_shift", "cgx_get_preconditioner_shift",
     "cgx_probe_get_precond_lowrank", "cgx_probe_precond_apply",
+    "cgx_solve_multi_pc", "cgx_probe_multi_pc_apply",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
@@ -157,6 +158,8 @@ def lib():
         L.cgx_probe_resident_test.argtypes = [vp, C.c_ulonglong, C.c_int]
         L.cgx_probe_get_p2p_epoch.argtypes = [vp, C.c_int, C.POINTER(C.c_ulonglong)]
         L.cgx_solve_multi.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_solve_multi_pc.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_probe_multi_pc_apply.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long]
         L.cgx_solve_shifted.argtypes = [vp, C.c_int, dp, dp, C.c_long, C.POINTER(Result)]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
@@ -460,17 +463,35 @@ class CGSolver:
         self._check(lib().cgx_solve(self._h, _dp(x), C.byref(res)))
         return res.as_dict()
 
-    def solve_multi(self, B, X=None):
-        """B: float64 array (k, n), one right-hand side per row; X: initial guesses of the same shape (None = zeros).
-        Returns (X, [k result dicts]): k independent CG solves on the current matrix, one pass over A per iteration."""
+    def _solve_block(self, entry, B, X):
         B = np.ascontiguousarray(B, dtype=np.float64)
         assert B.ndim == 2 and B.shape[1] == self.n(), B.shape
         X = np.zeros_like(B) if X is None else np.array(X, dtype=np.float64, copy=True, order="C")
         assert X.shape == B.shape, (X.shape, B.shape)
         k = B.shape[0]
         res = (Result * max(k, 1))()
-        self._check(lib().cgx_solve_multi(self._h, int(k), _dp(B), int(B.shape[1]), _dp(X), int(X.shape[1]), res))
+        self._check(entry(self._h, int(k), _dp(B), int(B.shape[1]), _dp(X), int(X.shape[1]), res))
         return X, [res[j].as_dict() for j in range(k)]
+
+    def solve_multi(self, B, X=None):
+        """B: float64 array (k, n), one right-hand side per row; X: initial guesses of the same shape (None = zeros).
+        Returns (X, [k result dicts]): k independent CG solves on the current matrix, one pass over A per iteration.
+        Refuses a preconditioner: solve_multi_pc takes it."""
+        return self._solve_block(lib().cgx_solve_multi, B, X)
+
+    def solve_multi_pc(self, B, X=None):
+        """solve_multi with the preconditioner that is set ("jacobi" with block 1, or "pivchol"): k independent preconditioned
+        CG solves, one pass over A per iteration, the inverse diagonal / the factor shared with solve().  With no preconditioner
+        set it is solve_multi, bit for bit."""
+        return self._solve_block(lib().cgx_solve_multi_pc, B, X)
+
+    def _probe_multi_pc_apply(self, R):
+        """Test hook: R float64 (k, n); returns Z with Z[j] = M^-1 R[j] through the preconditioned multi-vector update kernels."""
+        R = np.ascontiguousarray(R, dtype=np.float64)
+        assert R.ndim == 2 and R.shape[1] == self.n(), R.shape
+        Z = np.zeros_like(R)
+        self._check(lib().cgx_probe_multi_pc_apply(self._h, int(R.shape[0]), _dp(R), int(R.shape[1]), _dp(Z), int(Z.shape[1])))
+        return Z
 
     def solve_shifted(self, shifts):
         """shifts: sigma_j >= 0 (at most MAX_SHIFTS).  Returns (X, [result dicts]), X of shape (len(shifts), n): row j solves

@@ -110,6 +110,9 @@ void free_problem(cgx_ctx *ctx)
     (void)hipFree(ctx->multi);
     ctx->multi = nullptr;
     ctx->multi_bytes = 0;
+    (void)hipFree(ctx->multi_pc);
+    ctx->multi_pc = nullptr;
+    ctx->multi_pc_bytes = 0;
     (void)hipFree(ctx->shift);
     ctx->shift = nullptr;
     ctx->shift_bytes = 0;

@@ -107,12 +107,13 @@ __device__ __forceinline__ double block_sum(double v, double *lds /* >= WAVES do
 // p.Ap = sum of every K1 workgroup partial of every rank (cblas_ddot + MPI_Allreduce, cg.cc:105-106): the thread's share, to be
 // finished by block_sum<4>.  Every workgroup of every rank (K3 in all its forms, the low-rank, multi-right-hand-side and
 // multi-shift updates) folds the same partials in the same fixed order: bit-identical everywhere.  The partials of rank q are
-// the `count` doubles at tails + q * S; one contiguous run is nranks == 1.  All 256 threads of the workgroup.
+// the `count` doubles at tails + q * S; one contiguous run is nranks == 1.  All 256 threads of the workgroup (tid: the thread's index among
+// them, where a workgroup runs several such groups: cgx_multi_pc.hip).
 // ------------------------------------------------------------------------------------------------
 // One row per thread (k_update_xr): one flat index over (rank, partial).  With a few partials per rank (the chunk partials of a
 // multi-GPU run: n/512 in all) every thread has at most one or two loads, all in flight together -- a loop over the ranks with
 // one load each was a chain of P dependent round trips (5.9 us at P = 8 against 4.8 at P = 2 and 4, round 3).
-__device__ __forceinline__ double fold_pap(const double *tails, int nranks, int S, int count)
+__device__ __forceinline__ double fold_pap(const double *tails, int nranks, int S, int count, int tid = threadIdx.x)
 {
     const int total = nranks * count;
     auto at = [&](int f) {
@@ -121,7 +122,7 @@ __device__ __forceinline__ double fold_pap(const double *tails, int nranks, int 
         return tails[(long)q * S + (f - q * count)];
     };
     double cs = 0.0;
-    for (int f = threadIdx.x; f < total; f += 4 * 256) {   // four independent loads in flight (clamped, not branched around)
+    for (int f = tid; f < total; f += 4 * 256) {           // four independent loads in flight (clamped, not branched around)
         double a[4];
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -405,6 +406,96 @@ __device__ __forceinline__ void pc_store_partials(const SegView &zv, int wg, dou
     zv.base[zv.Sr + wg] = rz;
     zv.base[zv.S + wg] = rr;
 }
+
+// ------------------------------------------------------------------------------------------------
+// shared by the multi-vector K1 of cgx_multi.hip and cgx_multi_pc.hip (its body: cgx_multi_gemv.inc)
+// ------------------------------------------------------------------------------------------------
+constexpr int kMultiWaves = 8;
+constexpr int kMultiThreads = kMultiWaves * 64;
+constexpr int kMultiChunk = 256;                     // columns staged per chunk (2 steps of 128)
+constexpr int kMultiSteps = kMultiChunk / 128;
+
+// rows per wave for a kernel width: R * W <= 32 partial sums per lane; W = 16 takes one row (two spill: the staged P and the
+// unrolled LDS reads of 16 columns come on top of the sums)
+template <int W>
+struct MultiShape {
+    static constexpr int R = W <= 4 ? 8 : (W == 8 ? 4 : 1);
+};
+
+// Per column j: the head of iteration k (cg.cc:116-132 of iteration k-1) from the r.r partials rrp[j * g3 + 0 .. g3) -- PRE: and
+// the r.z partials rzp[j * g3 + 0 .. g3).  Run by one wave; every workgroup of the launch folds the same values in the same
+// order, so every workgroup takes the same decision.  Writes (workgroup 0 only, and nothing for a column that is already
+// frozen): rs (PRE: rho = r.z there, r.r in mp->rr), done, k_final.  Returns whether the column runs this iteration, and its beta.
+template <bool PRE>
+__device__ __forceinline__ bool multi_head(MultiScalars *ms, MultiPcScalars *mp, const double *__restrict__ rzp,
+                                           const double *__restrict__ rrp, int g3, int j, int k, double tol, bool writer,
+                                           double *beta)
+{
+    const int lane = threadIdx.x & 63;
+    const int done = ms->done[j];
+    const double rsold = ms->rs[j][(k > 0 ? k - 1 : 0) & 1];
+    const double *part = rrp + (long)j * g3;
+    if constexpr (!PRE) {
+        double v = 0.0;
+        for (int t = lane; t < g3; t += 256) {
+            double a[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int f = t + 64 * u;
+                const double val = part[f < g3 ? f : g3 - 1];
+                a[u] = f < g3 ? val : 0.0;
+            }
+            v += (a[0] + a[1]) + (a[2] + a[3]);
+        }
+        const double rsnew = wave_sum(v);                       // r.r, cg.cc:116-117 (k == 0: cg.cc:91-92)
+        *beta = 0.0;
+        if (done) return false;                                 // frozen: nothing is written any more
+        const bool first = writer && lane == 0;
+        if (k == 0) {                                           // p = r (cg.cc:85): beta = 0, p_old = 0
+            if (first) { ms->rs[j][0] = rsnew; ms->rs[j][1] = rsnew; }
+            return true;
+        }
+        if (first) ms->rs[j][k & 1] = rsnew;                    // rsold = rsnew, cg.cc:132
+        if (sqrt(rsnew) < tol) {                                // cg.cc:120-121: break before the p update
+            if (first) { ms->k_final[j] = k - 1; ms->done[j] = 1; }
+            return false;
+        }
+        *beta = rsnew / rsold;                                  // cg.cc:124
+        return true;
+    } else {
+        const double *partz = rzp + (long)j * g3;
+        double v = 0.0, vz = 0.0;
+        for (int t = lane; t < g3; t += 256) {
+            double a[4], z[4];
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int f = t + 64 * u, fc = f < g3 ? f : g3 - 1;
+                const double val = part[fc], valz = partz[fc];
+                a[u] = f < g3 ? val : 0.0;
+                z[u] = f < g3 ? valz : 0.0;
+            }
+            v += (a[0] + a[1]) + (a[2] + a[3]);
+            vz += (z[0] + z[1]) + (z[2] + z[3]);
+        }
+        const double rrnew = wave_sum(v);                       // r.r: the break and the report
+        const double rho = wave_sum(vz);                        // r.z: beta, and alpha's numerator in the update kernel
+        *beta = 0.0;
+        if (done) return false;
+        const bool first = writer && lane == 0;
+        if (k == 0) {                                           // p = z: beta = 0, p_old = 0
+            if (first) { ms->rs[j][0] = rho; ms->rs[j][1] = rho; mp->rr[j][0] = rrnew; mp->rr[j][1] = rrnew; }
+            return true;
+        }
+        if (first) { ms->rs[j][k & 1] = rho; mp->rr[j][k & 1] = rrnew; }
+        if (sqrt(rrnew) < tol) {                                // tol bounds the recursive residual, as without a preconditioner
+            if (first) { ms->k_final[j] = k - 1; ms->done[j] = 1; }
+            return false;
+        }
+        *beta = rho / rsold;
+        return true;
+    }
+}
+
 
 // p_new for the column pair (c, c+1); pad columns (>= n) stay exactly 0.
 // SINGLE (one shard): r is contiguous and zero padded up to lda, one 16-B load.

@@ -183,6 +183,10 @@ struct cgx_ctx {
     // partials and scalars of the multi kernels, apart from the single path's buffers; made on first use, freed with the problem
     double *multi = nullptr;
     size_t multi_bytes = 0;
+    // ... and what cgx_solve_multi_pc needs on top (Z, the r.z partials, the partials of L^T r, r.r's scalars): a block of its own,
+    // made on the first preconditioned multi call and freed with the problem, so that the plain block keeps its layout
+    double *multi_pc = nullptr;
+    size_t multi_pc_bytes = 0;
     // multi-shift CG (cgx_solve_shifted, cgx_shift_host.cpp): ONE device block holding the kMaxShifts-wide x and p of the shifts, the
     // block of the final verification and the shift scalars; made on first use, freed with the problem
     double *shift = nullptr;

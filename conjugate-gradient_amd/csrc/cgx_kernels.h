@@ -516,6 +516,34 @@ hipError_t launch_multi_close(MultiScalars *ms, const double *rrp, int n, int nr
 hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const double *b, const double *x, MultiScalars *ms,
                               hipStream_t s);
 
+// ---- several right-hand sides with a preconditioner (cgx_solve_multi_pc, cgx_multi_pc.hip) ----------------
+// Every column runs the recurrence of section 11 on the blocks above plus Z = M^-1 R.  MultiScalars keeps its layout: rs[j][] holds
+// rho_j = r_j.z_j (as Scalars::rs does under Jacobi), and r_j.r_j -- the break and the report -- lives in a block of its own.
+struct MultiPcScalars {
+    double rr[kMaxRhs][2];     // per column: r.r in rs's ping-pong (as Scalars::rr)
+};
+struct MultiPcArgs {
+    double *Z;                 // kMaxRhs x lda: z_j = M^-1 r_j (live columns only)
+    double *rzp;               // r.z partials, multi_update_grid(n) per column, beside MultiArgs::rrp
+    MultiPcScalars *mp;
+    const double *dinv;        // point Jacobi: the inverse diagonal (lda doubles); nullptr = pivoted Cholesky:
+    const double *L;           //   rank x lda, column-major at the matrix pitch
+    int rank;
+    const double *Cinv;        //   (delta I + L^T L)^-1 at pitch kLrLd
+    const LrHead *head;        //   delta
+    double *tpart;             //   kMaxRhs x lr_grid(n) x kLrLd: per column and 256-row tile the partials of t_j = L^T r_j
+};
+// K1m fused with the preconditioned head: g.r is Z, g.rrp the r.r partials; beta_j from r.z, the break from r.r.
+hipError_t launch_multi_gemv_pc(const MultiArgs &g, const MultiPcArgs &pc, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
+// K3m: launch_multi_update's work plus z and the r.z partials.  Jacobi: one launch (grid tiles x nrhs).  Pivoted Cholesky: two
+// launches of one workgroup per 256-row tile that serve all live columns, so the tile of L is read once per launch: the update
+// (x, r, r.r partials, partials of t_j) and the apply (t_j folded, u_j = C^-1 t_j, z_j, r.z partials).  init: r is taken as it is
+// (the set-up behind launch_multi_init, and the probe); p, Y, partials, x are not read then and every column < nrhs counts as live.
+hipError_t launch_multi_update_pc(int n, long lda, int nrhs, const double *p, const double *Y, const double *partials, int g1, double *x,
+                                  double *r, double *rrp, MultiScalars *ms, int parity, const MultiPcArgs &pc, bool init, hipStream_t s);
+hipError_t launch_multi_close_pc(MultiScalars *ms, const MultiPcArgs &pc, const double *rrp, int n, int nrhs, int k, double tol,
+                                 hipStream_t s);
+
 // ---- multi-shift CG: (A + sigma_j I) x_j = b for up to kMaxShifts shifts from one Krylov sequence (cgx_shift.hip) -------------
 // The seed is the single path's loop on A (K1 + K3, untouched); one kernel behind each K3 advances every shift.  X and P (the
 // x and p of the shifts) are column-major at pitch lda like the multi block: shift j at base + j * lda, zero padded up to lda.

@@ -13,12 +13,7 @@
 // A column whose break test passes is frozen: no later kernel writes its x, r, p or scalars; the others go on.  Columns
 // j >= nrhs of a kernel width (k = 3 runs the 4-wide kernels) are masked by nrhs, never by their values.
 //
-// K1m shape: 8 waves per workgroup, each wave owns R consecutive rows, the workgroup 8R.  The workgroup sweeps the columns in
-// chunks of kMultiChunk; the chunk of all W vectors is staged in LDS as [column j][kMultiChunk doubles], so that a lane's
-// 16-B read of (j, c..c+1) is conflict free across the wave, and every lane streams its R rows of A with one 16-B load per row
-// and 128-column step.  Every staged vector element serves the 8R rows of the workgroup; the A stream is the same as K1's.
-// Per row and column the sum order is fixed (lane: ascending chunks and steps, .x then .y; wave: wave_sum_rows), and it does
-// not depend on the column's position among the others, so permuting the columns permutes the results bit for bit.
+// The K1m shape and its sum orders: cgx_multi_gemv.inc (the body is shared with the preconditioned form, cgx_multi_pc.hip).
 #include "cgx_kernels.h"
 #include "cgx_device.h"
 
@@ -28,59 +23,7 @@ namespace cgx {
 
 namespace {
 
-constexpr int kMultiWaves = 8;
-constexpr int kMultiThreads = kMultiWaves * 64;
-constexpr int kMultiChunk = 256;                     // columns staged per chunk (2 steps of 128)
-constexpr int kMultiSteps = kMultiChunk / 128;
-
-// rows per wave for a kernel width: R * W <= 32 partial sums per lane; W = 16 takes one row (two spill: the staged P and the
-// unrolled LDS reads of 16 columns come on top of the sums)
-template <int W>
-struct MultiShape {
-    static constexpr int R = W <= 4 ? 8 : (W == 8 ? 4 : 1);
-};
-
-// Per column j: the head of iteration k (cg.cc:116-132 of iteration k-1) from the r.r partials rrp[j * g3 + 0 .. g3).  Run by
-// one wave; every workgroup of the launch folds the same values in the same order, so every workgroup takes the same decision.
-// Writes (workgroup 0 only, and nothing for a column that is already frozen): rs, done, k_final.  Returns whether the column
-// runs this iteration, and its beta.
-__device__ __forceinline__ bool multi_head(MultiScalars *ms, const double *__restrict__ rrp, int g3, int j, int k, double tol,
-                                           bool writer, double *beta)
-{
-    const int lane = threadIdx.x & 63;
-    const int done = ms->done[j];
-    const double rsold = ms->rs[j][(k > 0 ? k - 1 : 0) & 1];
-    const double *part = rrp + (long)j * g3;
-    double v = 0.0;
-    for (int t = lane; t < g3; t += 256) {
-        double a[4];
-#pragma unroll
-        for (int u = 0; u < 4; ++u) {
-            const int f = t + 64 * u;
-            const double val = part[f < g3 ? f : g3 - 1];
-            a[u] = f < g3 ? val : 0.0;
-        }
-        v += (a[0] + a[1]) + (a[2] + a[3]);
-    }
-    const double rsnew = wave_sum(v);                       // r.r, cg.cc:116-117 (k == 0: cg.cc:91-92)
-    *beta = 0.0;
-    if (done) return false;                                 // frozen: nothing is written any more
-    const bool first = writer && lane == 0;
-    if (k == 0) {                                           // p = r (cg.cc:85): beta = 0, p_old = 0
-        if (first) { ms->rs[j][0] = rsnew; ms->rs[j][1] = rsnew; }
-        return true;
-    }
-    if (first) ms->rs[j][k & 1] = rsnew;                    // rsold = rsnew, cg.cc:132
-    if (sqrt(rsnew) < tol) {                                // cg.cc:120-121: break before the p update
-        if (first) { ms->k_final[j] = k - 1; ms->done[j] = 1; }
-        return false;
-    }
-    *beta = rsnew / rsold;                                  // cg.cc:124
-    return true;
-}
-
-// K1m.  FUSED: iteration head, P = R + beta P_old staged (and stored once: chunk c by workgroup c mod grid), Y = A P, partials.
-// Plain: Y = A V for the nrhs columns of V, partials of V_j . Y_j.  Y, partials and p_new are written for live columns only.
+// K1m: the body is cgx_multi_gemv.inc with PRE = false (the plain head: one partial set per column).
 template <int W, bool FUSED>
 __global__ __launch_bounds__(kMultiThreads, 2) void k_multi_gemv(const double *__restrict__ A, long lda, int n, int nrhs,
                                                                  const double *__restrict__ v, double *__restrict__ p_new,
@@ -88,146 +31,10 @@ __global__ __launch_bounds__(kMultiThreads, 2) void k_multi_gemv(const double *_
                                                                  int g3, double *__restrict__ Y, double *__restrict__ partials,
                                                                  MultiScalars *ms, int k, double tol)
 {
-    constexpr int R = MultiShape<W>::R;
-    constexpr int ROWS = kMultiWaves * R;
-    constexpr int NV = R * W;
-    __shared__ d2 tile[2][W][kMultiChunk / 2];
-    __shared__ double red[kMultiWaves][NV];
-    __shared__ double s_beta[W];
-    __shared__ int s_live[W];
-
-    const int lane = threadIdx.x & 63;
-    const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // wave-uniform: the row pointers live in SGPRs
-    const int tid = threadIdx.x;
-
-    if constexpr (FUSED) {
-        for (int j = w; j < W; j += kMultiWaves) {
-            double beta = 0.0;
-            const bool live = j < nrhs && multi_head(ms, rrp, g3, j, k, tol, blockIdx.x == 0, &beta);
-            if (lane == 0) { s_beta[j] = beta; s_live[j] = live ? 1 : 0; }
-        }
-    } else {
-        if (tid < W) { s_beta[tid] = 0.0; s_live[tid] = tid < nrhs ? 1 : 0; }
-    }
-    __syncthreads();
-    int any = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j) any |= s_live[j];
-    if (FUSED && blockIdx.x == 0 && tid == 0 && !any && !ms->all_done) {
-        ms->all_done = 1;                                   // the host polls this word
-        ms->k_all = k - 1;
-    }
-    if (!any) return;                                       // every column has broken: the grid drains at once
-
-    const long row_w = (long)blockIdx.x * ROWS + (long)w * R;
-    const char *a_row[R];
-#pragma unroll
-    for (int i = 0; i < R; ++i) {
-        long row = row_w + i;
-        if (row > n - 1) row = n - 1;                       // tail workgroup: re-read the last row, result discarded
-        a_row[i] = reinterpret_cast<const char *>(A + row * lda);
-    }
-    double acc[NV];
-#pragma unroll
-    for (int i = 0; i < NV; ++i) acc[i] = 0.0;
-
-    const int ncols = (n + 1) & ~1;                         // pad columns up to lda are zero in A and in every vector
-    const int nchunks = (ncols + kMultiChunk - 1) / kMultiChunk;
-    constexpr int kStage = (W * kMultiChunk / 2 + kMultiThreads - 1) / kMultiThreads;   // 16-B pieces per thread and chunk
-    d2 st[kStage];
-
-    // the staged value of piece q of chunk c: (column j, 2 doubles); zero for a masked column and past n
-    auto stage_load = [&](int c) {
-#pragma unroll
-        for (int u = 0; u < kStage; ++u) {
-            const int q = tid + u * kMultiThreads;
-            const int j = q / (kMultiChunk / 2), cc = q % (kMultiChunk / 2);
-            const long col = (long)c * kMultiChunk + 2 * cc;
-            d2 val = {0.0, 0.0};
-            if (q < W * kMultiChunk / 2 && col < ncols && s_live[j]) {
-                const long off = (long)j * lda + col;
-                if constexpr (FUSED) {
-                    const d2 po = *reinterpret_cast<const d2 *>(v + off);
-                    const d2 rr = *reinterpret_cast<const d2 *>(r + off);
-                    val.x = fma(s_beta[j], po.x, rr.x);     // cg.cc:127-129
-                    val.y = fma(s_beta[j], po.y, rr.y);
-                } else {
-                    val = *reinterpret_cast<const d2 *>(v + off);
-                }
-            }
-            st[u] = val;
-        }
-    };
-    auto stage_store = [&](int c, int buf) {
-        const bool owner = FUSED && (c % (int)gridDim.x) == (int)blockIdx.x;
-#pragma unroll
-        for (int u = 0; u < kStage; ++u) {
-            const int q = tid + u * kMultiThreads;
-            if (q < W * kMultiChunk / 2) {
-                const int j = q / (kMultiChunk / 2), cc = q % (kMultiChunk / 2);
-                tile[buf][j][cc] = st[u];
-                const long col = (long)c * kMultiChunk + 2 * cc;
-                if (owner && col < ncols && s_live[j]) *reinterpret_cast<d2 *>(p_new + (long)j * lda + col) = st[u];   // stored once
-            }
-        }
-    };
-
-    stage_load(0);
-    stage_store(0, 0);
-    __syncthreads();
-    for (int c = 0; c < nchunks; ++c) {
-        d2 a[kMultiSteps][R];
-#pragma unroll
-        for (int s = 0; s < kMultiSteps; ++s) {
-            const int col = c * kMultiChunk + s * 128 + lane * 2;
-            const unsigned off = (unsigned)(col < ncols ? col : 0) * 8u;
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const d2 val = load_a<true>(reinterpret_cast<const double *>(a_row[i] + off));
-                a[s][i] = col < ncols ? val : d2{0.0, 0.0};
-            }
-        }
-        if (c + 1 < nchunks) stage_load(c + 1);
-        const int buf = c & 1;
-#pragma unroll
-        for (int s = 0; s < kMultiSteps; ++s) {
-#pragma unroll
-            for (int j = 0; j < W; ++j) {
-                const d2 p = tile[buf][j][s * 64 + lane];
-#pragma unroll
-                for (int i = 0; i < R; ++i) {
-                    acc[i * W + j] = fma(a[s][i].x, p.x, acc[i * W + j]);
-                    acc[i * W + j] = fma(a[s][i].y, p.y, acc[i * W + j]);
-                }
-            }
-        }
-        if (c + 1 < nchunks) stage_store(c + 1, buf ^ 1);
-        __syncthreads();
-    }
-
-    // every lane group of 64 / NV lanes holds the total of one (row, column) pair
-    const int vi = wave_sum_rows<NV>(acc, lane);
-    const int i = vi / W, j = vi % W;
-    const long row = row_w + i;
-    double pv = 0.0;
-    if ((lane & (64 / NV - 1)) == 0) {
-        if (row < n && s_live[j]) {
-            const double y = acc[0];
-            Y[(long)j * lda + row] = y;
-            const long off = (long)j * lda + row;
-            const double pr = FUSED ? fma(s_beta[j], v[off], r[off]) : v[off];   // the p_j[row] this launch staged
-            pv = pr * y;                                                          // cg.cc:105
-        }
-        red[w][vi] = pv;
-    }
-    __syncthreads();
-    if (tid < W && s_live[tid]) {
-        double s = 0.0;
-        for (int ww = 0; ww < kMultiWaves; ++ww)
-#pragma unroll
-            for (int ii = 0; ii < R; ++ii) s += red[ww][ii * W + tid];
-        partials[(long)tid * gridDim.x + blockIdx.x] = s;
-    }
+    constexpr bool PRE = false;
+    constexpr const double *rzp = nullptr;
+    constexpr MultiPcScalars *mp = nullptr;
+#include "cgx_multi_gemv.inc"
 }
 
 // K3m: workgroup (b, j) = rows [256 b, 256 b + 256) of column j.  p.Ap = fold of K1m's g1 partials of column j in K3's order,
@@ -286,7 +93,7 @@ __global__ __launch_bounds__(kMultiThreads) void k_multi_close(MultiScalars *ms,
     const int w = threadIdx.x >> 6;
     for (int j = w; j < nrhs; j += kMultiWaves) {
         double beta;
-        (void)multi_head(ms, rrp, g3, j, k, tol, true, &beta);
+        (void)multi_head<false>(ms, nullptr, nullptr, rrp, g3, j, k, tol, true, &beta);
     }
 }
 

@@ -1,8 +1,12 @@
-// cgx_multi_host.cpp -- cgx_solve_multi and cgx_probe_gemv_multi: the host side of the multi-vector kernels (cgx_multi.hip).
+// cgx_multi_host.cpp -- cgx_solve_multi, cgx_solve_multi_pc and cgx_probe_gemv_multi: the host side of the multi-vector kernels
+// (cgx_multi.hip; with a preconditioner cgx_multi_pc.hip).
 //
 // One GPU, dense storage.  The k-wide blocks live in ONE device allocation of the context (cgx_ctx::multi), apart from the single
 // path's per-shard buffers and state blocks, so that a multi solve changes nothing a single solve reads: neither the plan, nor
-// x / r / p, nor the scalar block.  It is made on the first multi call of a problem and freed with the problem.
+// x / r / p, nor the scalar block.  It is made on the first multi call of a problem and freed with the problem.  What the
+// preconditioned call needs on top (Z, the r.z partials, the partials of L^T r, r.r's scalars) is a second block of the same kind
+// (cgx_ctx::multi_pc), so the first keeps its layout.  The preconditioner itself -- the inverse diagonal, or L, C^-1 and delta -- is
+// the single path's, made by prepare_jacobi / prepare_lowrank once per matrix and shared in both directions.
 #include "cgx_internal.h"
 
 #include <algorithm>
@@ -40,6 +44,24 @@ size_t multi_layout(const cgx_ctx *ctx, double *base, MultiView *v)
     return c.bytes();
 }
 
+// The preconditioned call's own block.
+struct PcView {
+    double *Z;                      // kW x lda
+    double *rzp;                    // kW x multi_update_grid(n): the r.z partials
+    double *tpart;                  // kW x lr_grid(n) x kLrLd: the partials of t_j = L^T r_j (pivoted Cholesky)
+    cgx::MultiPcScalars *mp;
+};
+
+size_t pc_layout(const cgx_ctx *ctx, double *base, PcView *v)
+{
+    Carver c{base};
+    v->Z = c.take((size_t)kW * ctx->lda);
+    v->rzp = c.take((size_t)kW * cgx::multi_update_grid(ctx->n));
+    v->tpart = c.take((size_t)kW * cgx::multi_update_grid(ctx->n) * cgx::kLrLd);
+    v->mp = c.take_struct<cgx::MultiPcScalars>();
+    return c.bytes();
+}
+
 // The checks every multi entry point makes, in this order: context, problem, transport and storage, arguments.
 cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in, long ldin, const void *out, long ldout)
 {
@@ -58,6 +80,33 @@ cgx_status ensure_multi(cgx_ctx *ctx, MultiView *v)
     CGX_TRY(ensure_side_block(ctx, &ctx->multi, &ctx->multi_bytes, multi_layout(ctx, nullptr, v)));
     multi_layout(ctx, ctx->multi, v);
     return CGX_OK;
+}
+
+cgx_status ensure_multi_pc(cgx_ctx *ctx, PcView *v)
+{
+    CGX_TRY(ensure_side_block(ctx, &ctx->multi_pc, &ctx->multi_pc_bytes, pc_layout(ctx, nullptr, v)));
+    pc_layout(ctx, ctx->multi_pc, v);
+    return CGX_OK;
+}
+
+// What the preconditioned kernels take, for the context's kind (behind prepare_jacobi / prepare_lowrank).
+cgx::MultiPcArgs pc_args(const cgx_ctx *ctx, const PcView &pv)
+{
+    cgx::MultiPcArgs a{};
+    a.Z = pv.Z;
+    a.rzp = pv.rzp;
+    a.mp = pv.mp;
+    if (ctx->precond == CGX_PRECOND_JACOBI) {
+        a.dinv = ctx->shards[0].dinv;
+    } else {
+        const cgx::LrWork w = lr_work(ctx);
+        a.L = ctx->lr_L;
+        a.rank = ctx->lr_L_rank;
+        a.Cinv = w.C;
+        a.head = w.head;
+        a.tpart = pv.tpart;
+    }
+    return a;
 }
 
 cgx::MultiArgs plain_args(cgx_ctx *ctx, const MultiView &v, int nrhs, const double *vec)
@@ -89,33 +138,50 @@ cgx_status download(cgx_ctx *ctx, double *dst, long ld, const double *src, int n
     return CGX_OK;
 }
 
-// K1m fused of iteration k, event-timed where next_gemv_events says so (as run_gemv_fused, cgx_solve.cpp)
-cgx_status run_multi_fused(cgx_ctx *ctx, const MultiView &v, int nrhs, int k)
+// K1m fused of iteration k, event-timed where next_gemv_events says so (as run_gemv_fused, cgx_solve.cpp); pc: the preconditioned
+// head, p = z + beta p_old
+cgx_status run_multi_fused(cgx_ctx *ctx, const MultiView &v, int nrhs, int k, const cgx::MultiPcArgs *pc)
 {
     hipEvent_t e0, e1;
     CGX_TRY(next_gemv_events(ctx, &e0, &e1));
     cgx::MultiArgs g = plain_args(ctx, v, nrhs, v.P[k & 1]);
     g.p_new = v.P[(k + 1) & 1];
-    g.r = v.R;
+    g.r = pc ? pc->Z : v.R;
     g.rrp = v.rrp;
     g.k = k;
     g.tol = ctx->tol;
-    HIP_TRY(ctx, cgx::launch_multi_gemv(g, true, ctx->stream, e0, e1));
+    if (pc) HIP_TRY(ctx, cgx::launch_multi_gemv_pc(g, *pc, ctx->stream, e0, e1));
+    else HIP_TRY(ctx, cgx::launch_multi_gemv(g, true, ctx->stream, e0, e1));
     return CGX_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
+// The preconditioner of a preconditioned multi call, behind check_multi: the refusals of the single path's set-up with their status
+// and message, and -- once per matrix (rank, shift) -- the inverse diagonal or the factor, by the single path's own functions.
+cgx_status prepare_multi_pc(cgx_ctx *ctx, const char *name)
 {
-    CGX_TRY(check_multi(ctx, "cgx_solve_multi", nrhs, B, ldb, X, ldx));
-    if (ctx->precond != CGX_PRECOND_NONE)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_solve_multi: no preconditioner for several right-hand sides (cgx_set_preconditioner)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (ctx->precond == CGX_PRECOND_JACOBI) {
+        if (ctx->precond_block > 1)
+            return fail(ctx, CGX_ERR_UNSUPPORTED, std::string(name) + ": block Jacobi (cgx_set_preconditioner_block > 1) has no multi-vector "
+                                                                     "update kernel; point Jacobi and CGX_PRECOND_PIVCHOL have");
+        return prepare_jacobi(ctx);
+    }
+    if (ctx->precond == CGX_PRECOND_PIVCHOL) return prepare_lowrank(ctx);
+    return fail(ctx, CGX_ERR_UNSUPPORTED, std::string(name) + ": unknown preconditioner");
+}
+
+// THE multi solve: set-up, the polled loop, the final product and the results.  pre: every column runs the recurrence of DESIGN.md
+// section 11 with the context's preconditioner (already prepared); otherwise the plain one.  The preconditioner is the varying
+// part: which K1m head, which K3m, the launch behind the initial residual, which r.r the results read.
+cgx_status solve_multi_body(cgx_ctx *ctx, bool pre, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
+{
     MultiView v;
     CGX_TRY(ensure_multi(ctx, &v));
+    PcView pv{};
+    cgx::MultiPcArgs pc{};
+    if (pre) {
+        CGX_TRY(ensure_multi_pc(ctx, &pv));
+        pc = pc_args(ctx, pv);
+    }
     hipStream_t st = ctx->stream;
     const int n = ctx->n;
     const long lda = ctx->lda;
@@ -123,31 +189,39 @@ cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, do
     reset_gemv_stats(ctx);
     const double t_begin = wall_now();
 
-    // set-up, cg.cc:49-92 per column: r = b - A x0, p_old = 0, the r.r partials of iteration 0's head
+    // set-up, cg.cc:49-92 per column: r = b - A x0, p_old = 0, the r.r partials of iteration 0's head (pre: z0 and its partials)
     CGX_TRY(upload(ctx, v.B, B, ldb, nrhs));
     CGX_TRY(upload(ctx, v.X, X, ldx, nrhs));
     HIP_TRY(ctx, hipMemsetAsync(v.ms, 0, sizeof(cgx::MultiScalars), st));
+    if (pre) HIP_TRY(ctx, hipMemsetAsync(pv.mp, 0, sizeof(cgx::MultiPcScalars), st));
     HIP_TRY(ctx, hipMemsetAsync(v.P[0], 0, (size_t)nrhs * lda * sizeof(double), st));
     HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.X), false, st));
     HIP_TRY(ctx, cgx::launch_multi_init(n, lda, nrhs, v.B, v.Y, v.R, v.rrp, st));
+    if (pre) HIP_TRY(ctx, cgx::launch_multi_update_pc(n, lda, nrhs, nullptr, nullptr, nullptr, 0, nullptr, v.R, v.rrp, v.ms, 0, pc, true, st));
 
     // the loop cg.cc:95-137: K1m + K3m per iteration; all_done is polled every check_every iterations, one batch kept queued
     const double t0 = wall_now();
     auto iteration = [&](int i) -> cgx_status {
-        CGX_TRY(run_multi_fused(ctx, v, nrhs, i));
-        HIP_TRY(ctx, cgx::launch_multi_update(n, lda, nrhs, v.P[(i + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, i & 1, st));
+        CGX_TRY(run_multi_fused(ctx, v, nrhs, i, pre ? &pc : nullptr));
+        if (pre)
+            HIP_TRY(ctx, cgx::launch_multi_update_pc(n, lda, nrhs, v.P[(i + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, i & 1, pc, false, st));
+        else
+            HIP_TRY(ctx, cgx::launch_multi_update(n, lda, nrhs, v.P[(i + 1) & 1], v.Y, v.k1p, g1, v.X, v.R, v.rrp, v.ms, i & 1, st));
         return CGX_OK;
     };
     int k = 0;
     CGX_TRY(run_polled(ctx, &v.ms->all_done, ctx->max_iter, false, iteration, &k));   // (no device-side window: steps_device_ms stays 0)
     // the head of iteration k for the columns still running (cg.cc:117-121,132), then x and the DEBUG norms (cg.cc:140-151)
-    HIP_TRY(ctx, cgx::launch_multi_close(v.ms, v.rrp, n, nrhs, k, ctx->tol, st));
+    if (pre) HIP_TRY(ctx, cgx::launch_multi_close_pc(v.ms, pc, v.rrp, n, nrhs, k, ctx->tol, st));
+    else HIP_TRY(ctx, cgx::launch_multi_close(v.ms, v.rrp, n, nrhs, k, ctx->tol, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
     HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.X), false, st));
     HIP_TRY(ctx, cgx::launch_multi_norms(n, lda, nrhs, v.Y, v.B, v.X, v.ms, st));
     cgx::MultiScalars hs;
+    cgx::MultiPcScalars hp;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ms, sizeof hs, hipMemcpyDeviceToHost, st));
+    if (pre) HIP_TRY(ctx, hipMemcpyAsync(&hp, pv.mp, sizeof hp, hipMemcpyDeviceToHost, st));
     CGX_TRY(download(ctx, X, ldx, v.X, nrhs));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
@@ -164,14 +238,58 @@ cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, do
             o = base;
             const bool done = hs.done[j] != 0;
             const int k_exit = done ? hs.k_final[j] : k;
+            const double *rr = pre ? hp.rr[j] : hs.rs[j];               // pre: rs[] holds r.z, the report is sqrt(r.r)
             o.iterations = k_exit;
             o.converged = done ? 1 : 0;
-            o.residual_prev = std::sqrt(hs.rs[j][k_exit & 1]);          // sqrt(rsold) as printed, cg.cc:152-153
-            o.residual_last = done ? std::sqrt(hs.rs[j][(k_exit + 1) & 1]) : o.residual_prev;
+            o.residual_prev = std::sqrt(rr[k_exit & 1]);                // sqrt(rsold) as printed, cg.cc:152-153
+            o.residual_last = done ? std::sqrt(rr[(k_exit + 1) & 1]) : o.residual_prev;
             o.x_norm = std::sqrt(hs.norms[j][2]);
             o.rel_residual = std::sqrt(hs.norms[j][0]) / std::sqrt(hs.norms[j][1]);
         }
     }
+    return CGX_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+cgx_status cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
+{
+    CGX_TRY(check_multi(ctx, "cgx_solve_multi", nrhs, B, ldb, X, ldx));
+    if (ctx->precond != CGX_PRECOND_NONE)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, "cgx_solve_multi: no preconditioner for several right-hand sides (cgx_set_preconditioner)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return solve_multi_body(ctx, false, nrhs, B, ldb, X, ldx, res);
+}
+
+cgx_status cgx_solve_multi_pc(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res)
+{
+    CGX_TRY(check_multi(ctx, "cgx_solve_multi_pc", nrhs, B, ldb, X, ldx));
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const bool pre = ctx->precond != CGX_PRECOND_NONE;
+    if (pre) CGX_TRY(prepare_multi_pc(ctx, "cgx_solve_multi_pc"));
+    return solve_multi_body(ctx, pre, nrhs, B, ldb, X, ldx, res);
+}
+
+// TEST PROBE: Z_j = M^-1 R_j for nrhs caller's vectors (one per row) through the preconditioned multi path's own kernels, the
+// set-up form of K3m (Jacobi: one launch; pivoted Cholesky: update + apply).  Needs a preconditioner; prepares it like a solve.
+cgx_status cgx_probe_multi_pc_apply(cgx_ctx *ctx, int nrhs, const double *R, long ldr, double *Z, long ldz)
+{
+    CGX_TRY(check_multi(ctx, "cgx_probe_multi_pc_apply", nrhs, R, ldr, Z, ldz));
+    if (ctx->precond == CGX_PRECOND_NONE) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_multi_pc_apply: no preconditioner is set");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    CGX_TRY(prepare_multi_pc(ctx, "cgx_probe_multi_pc_apply"));
+    MultiView v;
+    PcView pv{};
+    CGX_TRY(ensure_multi(ctx, &v));
+    CGX_TRY(ensure_multi_pc(ctx, &pv));
+    const cgx::MultiPcArgs pc = pc_args(ctx, pv);
+    CGX_TRY(upload(ctx, v.R, R, ldr, nrhs));
+    HIP_TRY(ctx, cgx::launch_multi_update_pc(ctx->n, ctx->lda, nrhs, nullptr, nullptr, nullptr, 0, nullptr, v.R, v.rrp, v.ms, 0, pc, true,
+                                             ctx->stream));
+    CGX_TRY(download(ctx, Z, ldz, pv.Z, nrhs));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CGX_OK;
 }
 

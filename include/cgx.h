@@ -342,6 +342,18 @@ cgx_status  cgx_get_update_samples(cgx_ctx *ctx, double *ms_out, int cap, int *c
  * pointer, ldb < n, ldx < n or no problem set: CGX_ERR_BAD_ARG.  The single path's plan and state are left as they were. */
 #define CGX_MAX_RHS 16
 cgx_status  cgx_solve_multi(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res);
+/* cgx_solve_multi with the context's preconditioner: arguments, layout, checks and their order are those
+ * of cgx_solve_multi.  CGX_PRECOND_NONE: exactly what cgx_solve_multi runs, bit for bit.  CGX_PRECOND_JACOBI with block 1 and
+ * CGX_PRECOND_PIVCHOL: every column runs the preconditioned recurrence of cgx_solve (z = M^-1 r, p0 = z0, alpha = r.z / p.Ap with
+ * the safeguard, beta = r.z(new) / r.z(old), p = z + beta p) with its own scalars and its own break on sqrt(r.r) < tol;
+ * residual_prev / residual_last are sqrt(r.r).  The inverse diagonal / the factor is the single path's, made once per matrix
+ * (rank, shift) by whichever call comes first, and whatever a single solve refuses for the kind is refused here with the same
+ * status and message (gemv_variant 40000 / 50000, a K1 shape with split columns, rank > n, a matrix that is not positive
+ * definite, more than 262144 rows for CGX_PRECOND_PIVCHOL).  Block Jacobi (block > 1): CGX_ERR_UNSUPPORTED.  Column j's result
+ * depends on (A, b_j, x0_j, nrhs, the preconditioner's settings) only.
+ * cgx_solve_multi itself keeps refusing a preconditioner (CGX_ERR_UNSUPPORTED): callers rely on that refusal to learn that
+ * their setting would be ignored, so the preconditioned form is an entry point of its own. */
+cgx_status  cgx_solve_multi_pc(cgx_ctx *ctx, int nrhs, const double *B, long ldb, double *X, long ldx, cgx_result *res);
 /* The multi-vector K1 alone (plain form): Y_j = A P_j and pAp[j] = P_j . Y_j from the kernel's per-workgroup partials, added
  * in ascending order.  P, Y host arrays, one vector per row (P[j*ldp + i]); pAp: nrhs doubles.  Same scope as cgx_solve_multi. */
 cgx_status  cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long ldp, double *Y, long ldy, double *pAp);
@@ -444,6 +456,10 @@ cgx_status  cgx_probe_get_precond_blocks(cgx_ctx *ctx, int local_shard, double *
  * CGX_ERR_BAD_ARG. */
 cgx_status  cgx_probe_get_precond_lowrank(cgx_ctx *ctx, int *pivots, double *L_out, double *delta_used);
 cgx_status  cgx_probe_precond_apply(cgx_ctx *ctx, const double *r, double *z);
+/* TEST ONLY: Z_j = M^-1 R_j for nrhs vectors (one per row, as cgx_solve_multi_pc's B and X) through the set-up form of the
+ * preconditioned multi-vector update kernels.  Needs CGX_PRECOND_JACOBI (block 1) or CGX_PRECOND_PIVCHOL; makes the inverse
+ * diagonal / the factor if the current matrix has none yet. */
+cgx_status  cgx_probe_multi_pc_apply(cgx_ctx *ctx, int nrhs, const double *R, long ldr, double *Z, long ldz);
 /* Copy this shard's device row block (rows x n, dense, row-major) back to the host (banded storage is expanded). */
 cgx_status  cgx_probe_get_matrix_rows(cgx_ctx *ctx, int local_shard, double *A_out, int *row0, int *rows);
 

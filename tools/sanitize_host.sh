@@ -10,7 +10,7 @@ P=$R/conjugate-gradient_amd
 CL=/opt/rocm/lib/llvm/bin/clang++
 W=$(mktemp -d /tmp/cgx_san.XXXX)
 cd $W
-DEV="cgx_kernels cgx_csr cgx_p2p cgx_symv cgx_multi cgx_shift cgx_lowrank cgx_resident cgx_stream"   # the launchers the host objects call
+DEV="cgx_kernels cgx_csr cgx_p2p cgx_symv cgx_multi cgx_multi_pc cgx_shift cgx_lowrank cgx_resident cgx_stream"   # the launchers the host objects call
 make -C $P -s $(for f in $DEV; do echo build/$f.o; done)
 python3 - <<'PY'
 page = 4096
