@@ -40,8 +40,12 @@ EXPORTS = [
     "cgx_set_preconditioner_rank", "cgx_get_preconditioner_rank", "cgx_set_preconditioner_shift", "cgx_get_preconditioner_shift",
     "cgx_probe_get_precond_lowrank", "cgx_probe_precond_apply",
     "cgx_solve_multi_pc", "cgx_probe_multi_pc_apply",
+    "cgx_lanczos", "cgx_trace_slq", "cgx_tridiag_quadrature",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
+MAX_LANCZOS_STEPS = 1024   # CGX_MAX_LANCZOS_STEPS
+MAX_PROBES = 256           # CGX_MAX_PROBES
+SLQ_LOG, SLQ_INV = 0, 1    # cgx_trace_slq's fn
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 PRECOND_PIVCHOL = 2                   # the pivoted-Cholesky low-rank factor: one GPU, dense storage
@@ -161,6 +165,9 @@ def lib():
         L.cgx_solve_multi_pc.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
         L.cgx_probe_multi_pc_apply.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long]
         L.cgx_solve_shifted.argtypes = [vp, C.c_int, dp, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_lanczos.argtypes = [vp, C.c_int, C.c_int, dp, C.c_long, dp, dp, ip]
+        L.cgx_trace_slq.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, dp, C.c_long, dp, dp, dp, dp]
+        L.cgx_tridiag_quadrature.argtypes = [C.c_int, dp, dp, dp, dp]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
         L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
@@ -503,6 +510,42 @@ class CGSolver:
         res = (Result * max(k, 1))()
         self._check(lib().cgx_solve_shifted(self._h, int(k), _dp(sig), _dp(X), int(n), res))
         return X, [res[j].as_dict() for j in range(k)]
+
+    def lanczos(self, V0, steps):
+        """V0: float64 array (k, n), one start vector per row (k <= MAX_RHS).  Returns (alpha, beta, steps_done): the coefficients
+        of `steps` steps of the Lanczos recurrence on the current matrix from every start vector, one pass over A per step;
+        alpha, beta of shape (k, steps), zero at t >= steps_done[j] (a column that reached an invariant subspace stops early)."""
+        V0 = np.ascontiguousarray(V0, dtype=np.float64)
+        assert V0.ndim == 2 and V0.shape[1] == self.n(), V0.shape
+        k, steps = V0.shape[0], int(steps)
+        alpha = np.zeros((max(k, 1), max(steps, 1)), dtype=np.float64)
+        beta = np.zeros_like(alpha)
+        done = np.zeros(max(k, 1), dtype=np.int32)
+        self._check(lib().cgx_lanczos(self._h, int(k), steps, _dp(V0), int(V0.shape[1]), _dp(alpha), _dp(beta),
+                                      done.ctypes.data_as(C.POINTER(C.c_int))))
+        return alpha[:k, :steps], beta[:k, :steps], done[:k]
+
+    def _trace_slq(self, fn, probes, steps, seed, Z):
+        if Z is not None:
+            Z = np.ascontiguousarray(Z, dtype=np.float64)
+            assert Z.ndim == 2 and Z.shape[1] == self.n(), Z.shape
+            probes = Z.shape[0]
+        est, err = C.c_double(), C.c_double()
+        per = np.zeros(max(int(probes), 1), dtype=np.float64)
+        ritz = np.zeros(2, dtype=np.float64)
+        self._check(lib().cgx_trace_slq(self._h, int(fn), int(probes), int(steps), int(seed), None if Z is None else _dp(Z),
+                                        0 if Z is None else int(Z.shape[1]), C.byref(est), C.byref(err), _dp(per), _dp(ritz)))
+        return {"estimate": est.value, "std_error": err.value, "per_probe": per[:int(probes)], "ritz_min": ritz[0], "ritz_max": ritz[1]}
+
+    def logdet(self, probes=16, steps=100, seed=1, Z=None):
+        """log det of the current (symmetric positive definite, dense) matrix by stochastic Lanczos quadrature: `probes` Rademacher
+        vectors made by the library from `seed`, or the rows of Z; `steps` Lanczos steps each.  Returns a dict: estimate, std_error
+        (sample standard deviation / sqrt(probes)), per_probe, ritz_min, ritz_max (the extreme Ritz values over all probes)."""
+        return self._trace_slq(SLQ_LOG, probes, steps, seed, Z)
+
+    def trace_inv(self, probes=16, steps=100, seed=1, Z=None):
+        """tr(A^-1) of the current matrix, as logdet."""
+        return self._trace_slq(SLQ_INV, probes, steps, seed, Z)
 
     def probe_gemv_multi(self, P):
         """P: float64 array (k, n).  Returns (Y, pAp): Y[j] = A P[j] from the multi-vector K1, pAp[j] = P[j] . Y[j]."""

@@ -191,6 +191,10 @@ struct cgx_ctx {
     // block of the final verification and the shift scalars; made on first use, freed with the problem
     double *shift = nullptr;
     size_t shift_bytes = 0;
+    // Lanczos quadrature (cgx_lanczos, cgx_trace_slq, cgx_lanczos_host.cpp): ONE device block holding the two kMaxRhs-wide vector
+    // blocks of the recurrence, Y, the partials, the alpha / beta histories and the scalars; made on first use, freed with the problem
+    double *lanczos = nullptr;
+    size_t lanczos_bytes = 0;
 
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 

@@ -590,4 +590,38 @@ hipError_t launch_shift_close(ShiftScalars *ss, const double *rrp, int nrr, int 
 hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, const double *b, const double *X, ShiftScalars *ss,
                               hipStream_t s);
 
+// ---- multi-vector Lanczos for Gauss quadrature (cgx_lanczos, cgx_trace_slq; cgx_lanczos.hip) -----------
+// Up to kMaxRhs three-term recurrences side by side, blocks laid out as the multi kernels' (column j at base + j * lda, zero padded
+// up to lda).  A step is the plain K1m (launch_multi_gemv, fused = false) on the not yet normalised w, then launch_lanczos_step.
+constexpr int kMaxLanczosSteps = 1024;         // = CGX_MAX_LANCZOS_STEPS
+constexpr int kLanczosLive = 0x7fffffff;       // LanczosScalars::m of a column that is still running
+struct LanczosScalars {
+    double amax[kMaxRhs][2];   // max |alpha_s| over s < t at [t & 1]: step t reads that slot and writes the other
+    double z2[kMaxRhs];        // ||V0_j||^2
+    int    m[kMaxRhs];         // steps the column made before it was frozen (kLanczosLive: running).  A step number, not a flag:
+                               // workgroup 0 of step t writes t while the others still read, and both values mean "decides in t"
+    int    bad[kMaxRhs];       // the start vector has norm 0 or is not finite (m = -1: no step runs)
+};
+struct LanczosArgs {
+    int n, nvec;
+    long lda;
+    double *w;                 // in: the unnormalised w_t;   out: v_t = w_t / beta_(t-1)
+    double *vprev;             // in: v_(t-1);                out: the unnormalised w_(t+1)
+    const double *Y;           // K1m's A w_t
+    const double *k1p;         // K1m's w_t . A w_t partials, g1 per column
+    int g1;
+    const double *ww_in;       // ||w_t||^2 partials, multi_update_grid(n) per column
+    double *ww_out;            // ||w_(t+1)||^2 partials
+    LanczosScalars *ls;
+    double *alpha, *beta;      // the histories: kMaxRhs rows of kMaxLanczosSteps
+    int t;
+};
+// Per column (one workgroup each): ||V0_j||^2 in a fixed order as the column's one ||w||^2 partial, v_(-1) = 0, the scalars reset;
+// a zero or non-finite column is marked bad and never runs.
+hipError_t launch_lanczos_init(int n, long lda, int nvec, const double *w, double *vprev, double *ww, LanczosScalars *ls, hipStream_t s);
+// Step t behind K1m: beta_(t-1) and the breakdown test, alpha_t, v_t over w, w_(t+1) over v_(t-1), the next ||w||^2 partials.
+hipError_t launch_lanczos_step(const LanczosArgs &a, hipStream_t s);
+// Behind the last step: beta_(steps-1) and m = steps for the columns still running.
+hipError_t launch_lanczos_close(int n, int nvec, int steps, const double *ww, LanczosScalars *ls, double *beta, hipStream_t s);
+
 }  // namespace cgx

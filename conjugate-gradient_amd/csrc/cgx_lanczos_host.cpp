@@ -1,0 +1,282 @@
+// cgx_lanczos_host.cpp -- cgx_lanczos, cgx_trace_slq and cgx_tridiag_quadrature: the host side of the multi-vector Lanczos
+// recurrence (cgx_lanczos.hip) and stochastic Lanczos quadrature on top of it.
+//
+// One GPU, dense storage.  The blocks live in ONE device allocation of the context (cgx_ctx::lanczos), apart from the single
+// path's buffers and from the multi blocks, made on the first call of a problem and freed with it.  A step is two launches -- the
+// plain multi-vector K1 of cgx_multi.hip as it is, then k_lanczos_step -- and nothing is polled: the steps are queued behind each
+// other and one synchronisation ends them.
+#include "cgx_internal.h"
+
+#include <cmath>
+#include <cstring>
+#include <string>
+#include <vector>
+
+using namespace cgxi;
+
+namespace {
+
+constexpr int kW = cgx::kMaxRhs;
+constexpr int kSlqBatch = 8;   // probes per Lanczos run: the width at which K1m is cheapest per column
+
+struct LanczosView {
+    double *V[2], *Y;               // kW x lda each (column j at + j * lda)
+    double *k1p;                    // kW x k1p_stride(n): K1m's w.Aw partials
+    double *wwp[2];                 // kW x multi_update_grid(n) each: the ||w||^2 partials, ping-pong over the steps
+    double *alpha, *beta;           // kW x kMaxLanczosSteps each: the histories
+    cgx::LanczosScalars *ls;
+};
+
+size_t lanczos_layout(const cgx_ctx *ctx, double *base, LanczosView *v)
+{
+    const size_t vec = (size_t)kW * ctx->lda;
+    Carver c{base};
+    v->V[0] = c.take(vec);
+    v->V[1] = c.take(vec);
+    v->Y = c.take(vec);
+    v->k1p = c.take((size_t)kW * k1p_stride(ctx->n));
+    v->wwp[0] = c.take((size_t)kW * cgx::multi_update_grid(ctx->n));
+    v->wwp[1] = c.take((size_t)kW * cgx::multi_update_grid(ctx->n));
+    v->alpha = c.take((size_t)kW * cgx::kMaxLanczosSteps);
+    v->beta = c.take((size_t)kW * cgx::kMaxLanczosSteps);
+    v->ls = c.take_struct<cgx::LanczosScalars>();
+    return c.bytes();
+}
+
+// The checks both entry points make, in this order: context, problem, transport, storage, preconditioner, steps.
+cgx_status check_lanczos(cgx_ctx *ctx, const char *name, int steps)
+{
+    const std::string fn(name);
+    CGX_TRY(check_one_gpu_call(ctx, fn));
+    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    if (ctx->precond != CGX_PRECOND_NONE)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": a preconditioner is set and would be ignored (cgx_set_preconditioner)");
+    if (steps < 1 || steps > CGX_MAX_LANCZOS_STEPS || steps > ctx->n)
+        return fail(ctx, CGX_ERR_BAD_ARG, fn + ": steps must be 1 .. min(n, CGX_MAX_LANCZOS_STEPS)");
+    return CGX_OK;
+}
+
+// THE recurrence: nvec start vectors (one per row of V0, pitch ldv) through `steps` steps.  alpha, beta: nvec rows of `steps`
+// doubles, zero at t >= m[j]; z2[j] = ||V0_j||^2 as the device summed it.  col0: the number of row 0 in the caller's own count,
+// for the message about a bad start vector.
+cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, const double *V0, long ldv, int col0, double *alpha,
+                       double *beta, int *m, double *z2)
+{
+    LanczosView v;
+    CGX_TRY(ensure_side_block(ctx, &ctx->lanczos, &ctx->lanczos_bytes, lanczos_layout(ctx, nullptr, &v)));
+    lanczos_layout(ctx, ctx->lanczos, &v);
+    hipStream_t st = ctx->stream;
+    const int n = ctx->n;
+    const long lda = ctx->lda;
+    const int g1 = cgx::multi_gemv_grid(n, cgx::multi_width(nvec));
+
+    HIP_TRY(ctx, hipMemcpy2DAsync(v.V[0], (size_t)lda * sizeof(double), V0, (size_t)ldv * sizeof(double), (size_t)n * sizeof(double), nvec,
+                                  hipMemcpyHostToDevice, st));
+    HIP_TRY(ctx, cgx::launch_lanczos_init(n, lda, nvec, v.V[0], v.V[1], v.wwp[0], v.ls, st));
+    for (int t = 0; t < steps; ++t) {
+        double *w = v.V[t & 1], *vprev = v.V[(t + 1) & 1];
+        cgx::MultiArgs g{};
+        g.A = ctx->shards[0].A;
+        g.lda = lda;
+        g.n = n;
+        g.nrhs = nvec;
+        g.v = w;
+        g.Y = v.Y;
+        g.partials = v.k1p;
+        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
+        cgx::LanczosArgs a{};
+        a.n = n;
+        a.nvec = nvec;
+        a.lda = lda;
+        a.w = w;
+        a.vprev = vprev;
+        a.Y = v.Y;
+        a.k1p = v.k1p;
+        a.g1 = g1;
+        a.ww_in = v.wwp[t & 1];
+        a.ww_out = v.wwp[(t + 1) & 1];
+        a.ls = v.ls;
+        a.alpha = v.alpha;
+        a.beta = v.beta;
+        a.t = t;
+        HIP_TRY(ctx, cgx::launch_lanczos_step(a, st));
+    }
+    HIP_TRY(ctx, cgx::launch_lanczos_close(n, nvec, steps, v.wwp[steps & 1], v.ls, v.beta, st));
+    cgx::LanczosScalars hs;
+    HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ls, sizeof hs, hipMemcpyDeviceToHost, st));
+    const size_t row = (size_t)steps * sizeof(double), pitch = (size_t)cgx::kMaxLanczosSteps * sizeof(double);
+    HIP_TRY(ctx, hipMemcpy2DAsync(alpha, row, v.alpha, pitch, row, nvec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpy2DAsync(beta, row, v.beta, pitch, row, nvec, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+
+    for (int j = 0; j < nvec; ++j)
+        if (hs.bad[j])
+            return fail(ctx, CGX_ERR_BAD_ARG, std::string(name) + ": start vector " + std::to_string(col0 + j) + " has norm 0 or is not finite");
+    for (int j = 0; j < nvec; ++j) {
+        m[j] = hs.m[j];
+        z2[j] = hs.z2[j];
+        for (int t = m[j]; t < steps; ++t) alpha[(size_t)j * steps + t] = beta[(size_t)j * steps + t] = 0.0;
+    }
+    return CGX_OK;
+}
+
+// sqrt(a^2 + b^2) without overflow (the QL sweep's plane rotations)
+double pythag(double a, double b) { return std::hypot(a, b); }
+
+// Implicit symmetric QL with Wilkinson's shift on (d, e), carrying the FIRST ROW z of the eigenvector matrix along: the rotations
+// of a sweep are applied to z alone, so the work is O(m^2) and nothing m x m is held.  e[i] couples i and i + 1; e[m-1] is work space.
+bool ql_first_row(int m, double *d, double *e, double *z)
+{
+    for (int l = 0; l < m; ++l) {
+        int iter = 0, mm;
+        do {
+            for (mm = l; mm < m - 1; ++mm) {
+                const double dd = std::fabs(d[mm]) + std::fabs(d[mm + 1]);
+                if (std::fabs(e[mm]) + dd == dd) break;
+            }
+            if (mm != l) {
+                if (iter++ == 60) return false;
+                double g = (d[l + 1] - d[l]) / (2.0 * e[l]);
+                double r = pythag(g, 1.0);
+                g = d[mm] - d[l] + e[l] / (g + std::copysign(r, g));
+                double s = 1.0, c = 1.0, p = 0.0;
+                int i;
+                for (i = mm - 1; i >= l; --i) {
+                    double f = s * e[i];
+                    const double b = c * e[i];
+                    r = pythag(f, g);
+                    e[i + 1] = r;
+                    if (r == 0.0) {
+                        d[i + 1] -= p;
+                        e[mm] = 0.0;
+                        break;
+                    }
+                    s = f / r;
+                    c = g / r;
+                    g = d[i + 1] - p;
+                    r = (d[i] - g) * s + 2.0 * c * b;
+                    p = s * r;
+                    d[i + 1] = g + p;
+                    g = c * r - b;
+                    f = z[i + 1];
+                    z[i + 1] = s * z[i] + c * f;
+                    z[i] = c * z[i] - s * f;
+                }
+                if (r == 0.0 && i >= l) continue;
+                d[l] -= p;
+                e[l] = g;
+                e[mm] = 0.0;
+            }
+        } while (mm != l);
+    }
+    return true;
+}
+
+// nodes ascending and weights of the m-point rule; the scratch vectors are the caller's so that a batch allocates once
+bool gauss_rule(int m, const double *alpha, const double *beta, double *theta, double *weight, std::vector<double> &work, std::vector<int> &idx)
+{
+    work.assign((size_t)3 * m, 0.0);
+    idx.resize((size_t)m);
+    double *d = work.data(), *e = d + m, *z = e + m;
+    for (int i = 0; i < m; ++i) {
+        d[i] = alpha[i];
+        if (i + 1 < m) e[i] = beta[i];
+        idx[i] = i;
+    }
+    z[0] = 1.0;
+    if (!ql_first_row(m, d, e, z)) return false;
+    std::sort(idx.begin(), idx.end(), [&](int a, int b) { return d[a] < d[b] || (d[a] == d[b] && a < b); });
+    for (int i = 0; i < m; ++i) {
+        theta[i] = d[idx[i]];
+        weight[i] = z[idx[i]] * z[idx[i]];
+    }
+    return true;
+}
+
+// The Rademacher sign of element i of library probe j (include/cgx.h): the top bit of a counter-based hash.
+double rademacher(unsigned long long seed_mixed, unsigned long long j, unsigned long long i)
+{
+    return (cgx::hash_mix64(seed_mixed ^ ((j << 32) | i)) >> 63) ? -1.0 : 1.0;
+}
+
+}  // namespace
+
+extern "C" {
+
+cgx_status cgx_tridiag_quadrature(int m, const double *alpha, const double *beta, double *theta, double *weight)
+{
+    if (m < 1 || !alpha || !theta || !weight || (m > 1 && !beta)) return CGX_ERR_BAD_ARG;
+    for (int i = 0; i < m; ++i)
+        if (!std::isfinite(alpha[i]) || (i + 1 < m && !std::isfinite(beta[i]))) return CGX_ERR_BAD_ARG;
+    std::vector<double> e;
+    std::vector<int> idx;
+    return gauss_rule(m, alpha, beta, theta, weight, e, idx) ? CGX_OK : CGX_ERR_UNSUPPORTED;   // (no convergence in 60 sweeps per value)
+}
+
+cgx_status cgx_lanczos(cgx_ctx *ctx, int nvec, int steps, const double *V0, long ldv, double *alpha, double *beta, int *steps_done)
+{
+    CGX_TRY(check_lanczos(ctx, "cgx_lanczos", steps));
+    if (nvec < 1 || nvec > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_lanczos: nvec must be 1 .. CGX_MAX_RHS");
+    if (!V0 || !alpha || !beta || !steps_done) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_lanczos: null pointer");
+    if (ldv < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_lanczos: leading dimension smaller than n");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    double z2[kW];
+    return lanczos_run(ctx, "cgx_lanczos", nvec, steps, V0, ldv, 0, alpha, beta, steps_done, z2);
+}
+
+cgx_status cgx_trace_slq(cgx_ctx *ctx, int fn, int nprobe, int steps, unsigned long long seed, const double *Z, long ldz,
+                         double *estimate, double *std_error, double *per_probe, double *ritz)
+{
+    CGX_TRY(check_lanczos(ctx, "cgx_trace_slq", steps));
+    if (fn != CGX_SLQ_LOG && fn != CGX_SLQ_INV) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: fn must be CGX_SLQ_LOG or CGX_SLQ_INV");
+    if (nprobe < 1 || nprobe > CGX_MAX_PROBES) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: nprobe must be 1 .. CGX_MAX_PROBES");
+    if (!estimate || !std_error) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: null pointer");
+    if (Z && ldz < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: leading dimension smaller than n");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    const int n = ctx->n;
+    const unsigned long long sm = cgx::hash_mix64(seed);
+    std::vector<double> block, value((size_t)nprobe), alpha((size_t)kSlqBatch * steps), beta((size_t)kSlqBatch * steps);
+    std::vector<double> theta((size_t)steps), weight((size_t)steps), scratch;
+    std::vector<int> idx;
+    if (!Z) block.resize((size_t)kSlqBatch * n);
+    double lo = HUGE_VAL, hi = -HUGE_VAL;
+    for (int j0 = 0; j0 < nprobe; j0 += kSlqBatch) {
+        const int nb = std::min(kSlqBatch, nprobe - j0);
+        if (!Z)
+            for (int j = 0; j < nb; ++j)
+                for (int i = 0; i < n; ++i) block[(size_t)j * n + i] = rademacher(sm, (unsigned long long)(j0 + j), (unsigned long long)i);
+        int m[kSlqBatch];
+        double z2[kSlqBatch];
+        CGX_TRY(lanczos_run(ctx, "cgx_trace_slq", nb, steps, Z ? Z + (size_t)j0 * ldz : block.data(), Z ? ldz : (long)n, j0, alpha.data(),
+                            beta.data(), m, z2));
+        for (int j = 0; j < nb; ++j) {
+            const double *a = alpha.data() + (size_t)j * steps, *b = beta.data() + (size_t)j * steps;
+            bool finite = m[j] >= 1;
+            for (int t = 0; t < m[j] && finite; ++t) finite = std::isfinite(a[t]) && (t + 1 >= m[j] || std::isfinite(b[t]));
+            if (!finite || !gauss_rule(m[j], a, b, theta.data(), weight.data(), scratch, idx))
+                return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: the Lanczos coefficients of probe " + std::to_string(j0 + j) +
+                                                      " are not finite, or their Jacobi matrix has no eigen-decomposition");
+            if (!(theta[0] > 0.0))
+                return fail(ctx, CGX_ERR_BAD_ARG, "cgx_trace_slq: matrix is not positive definite (Ritz value " + std::to_string(theta[0]) +
+                                                      " from probe " + std::to_string(j0 + j) + ")");
+            double q = 0.0;
+            for (int i = 0; i < m[j]; ++i) q += weight[i] * (fn == CGX_SLQ_LOG ? std::log(theta[i]) : 1.0 / theta[i]);   // ascending theta
+            value[(size_t)j0 + j] = z2[j] * q;
+            lo = std::min(lo, theta[0]);
+            hi = std::max(hi, theta[m[j] - 1]);
+        }
+    }
+    double mean = 0.0;
+    for (int j = 0; j < nprobe; ++j) mean += value[j];
+    mean /= nprobe;
+    double var = 0.0;
+    for (int j = 0; j < nprobe; ++j) var += (value[j] - mean) * (value[j] - mean);
+    *estimate = mean;
+    *std_error = nprobe > 1 ? std::sqrt(var / (nprobe - 1)) / std::sqrt((double)nprobe) : 0.0;
+    if (per_probe) memcpy(per_probe, value.data(), (size_t)nprobe * sizeof(double));
+    if (ritz) { ritz[0] = lo; ritz[1] = hi; }
+    return CGX_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,10 @@
 // in OUTFILE is written as ever; one line per shift follows on stdout.  One GPU, dense or --csr, no --jacobi.
 // `--pivchol K [--pivchol-shift D]` (NOT a reference mode) solves with the rank-K pivoted-Cholesky preconditioner plus shift
 // (include/cgx.h CGX_PRECOND_PIVCHOL; D = 0 or absent: the automatic shift): one GPU, dense storage, not with --jacobi.
+// `--logdet P[,M]` (NOT a reference mode) estimates log det of the matrix instead of solving (include/cgx.h cgx_trace_slq): stochastic
+// Lanczos quadrature with P Rademacher probes (1 ... 256) of M Lanczos steps each (default 100, at most min(n, 1024)).  The timing
+// line in OUTFILE is written as ever; one line with the estimate, its standard error and the extreme Ritz values follows on stdout.
+// One GPU, dense storage, no preconditioner, not with --shifts; the matrix must be symmetric positive definite.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -32,6 +36,7 @@
 #include <cstring>
 #include <fstream>
 #include <functional>
+#include <iomanip>
 #include <iostream>
 #include <memory>
 #include <mutex>
@@ -155,6 +160,9 @@ int usage(const char *prog)
               << "         --shifts s0,s1,...       opt-in, not in the reference: solve (A + s I) x = b for up to 16 shifts s >= 0 in\n"
               << "                                  one Krylov sequence (multi-shift CG) instead of the plain solve; one GPU, dense\n"
               << "                                  or --csr, not with --jacobi; prints one line per shift\n"
+              << "         --logdet P[,M]           opt-in, not in the reference: estimate log det A instead of solving, by stochastic\n"
+              << "                                  Lanczos quadrature with P probes (1 ... 256) of M steps (default 100); one GPU,\n"
+              << "                                  dense storage, no preconditioner, not with --shifts; prints one line\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -179,6 +187,7 @@ int main(int argc, char **argv)
     bool have_pivchol_shift = false;
     std::vector<double> shifts;
     bool shifted = false;
+    int logdet_probes = 0, logdet_steps = 100;   // --logdet P[,M] (0 probes: off)
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -224,6 +233,17 @@ int main(int argc, char **argv)
                 shifts.push_back(v);
             }
         }
+        else if (a == "--logdet" && i + 1 < argc) {
+            const std::string arg(argv[++i]);
+            const size_t comma = arg.find(',');
+            const bool ok = parse_int(arg.substr(0, comma), &logdet_probes) &&
+                            (comma == std::string::npos || parse_int(arg.substr(comma + 1), &logdet_steps));
+            if (!ok || logdet_probes < 1 || logdet_probes > CGX_MAX_PROBES || logdet_steps < 1 || logdet_steps > CGX_MAX_LANCZOS_STEPS) {
+                std::cerr << argv[0] << ": --logdet takes P[,M] with 1 <= P <= " << CGX_MAX_PROBES << " probes and 1 <= M <= "
+                          << CGX_MAX_LANCZOS_STEPS << " steps, not '" << arg << "'\n";
+                return usage(argv[0]);
+            }
+        }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -248,6 +268,10 @@ int main(int argc, char **argv)
     }
     if (pivchol && jacobi) {
         std::cerr << argv[0] << ": --pivchol and --jacobi are two preconditioners: give one of them\n";
+        return usage(argv[0]);
+    }
+    if (logdet_probes && (shifted || jacobi || pivchol)) {
+        std::cerr << argv[0] << ": --logdet runs without a preconditioner and not together with --shifts\n";
         return usage(argv[0]);
     }
     if (ngpu < 1) ngpu = 1;
@@ -477,7 +501,13 @@ int main(int argc, char **argv)
 
         auto t1 = clk::now();                                // only solve() is timed, cg_main.cc:53-55
         std::vector<double> x_shifted;                       // --shifts: one solution per shift
-        if (shifted) solver.solve_shifted(shifts, x_shifted);
+        double slq[4] = {0, 0, 0, 0};                        // --logdet: estimate, standard error, smallest / largest Ritz value
+        if (logdet_probes) {
+            if (cgx_trace_slq(solver.context(), CGX_SLQ_LOG, logdet_probes, logdet_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
+                              &slq[2]) != CGX_OK)
+                throw std::runtime_error(std::string("--logdet: ") + cgx_last_error(solver.context()));
+        }
+        else if (shifted) solver.solve_shifted(shifts, x_shifted);
         else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
         else solver.solve(x_d);
         second elapsed = clk::now() - t1;
@@ -490,6 +520,10 @@ int main(int argc, char **argv)
                 std::cout << "Time for CG (dense solver)  = " << elapsed.count() << " [s]\n";   // code/CUDA/cg_main.cc:54
                 outfile << legacy_nt << "," << legacy_bw << "," << elapsed.count() << std::endl;   // :59
             }
+            if (logdet_probes)
+                std::cout << "\t[LOGDET] probes = " << logdet_probes << ", steps = " << logdet_steps << ", log det A = " << std::setprecision(12)
+                          << slq[0] << ", standard error = " << std::setprecision(6) << slq[1] << ", Ritz values in [" << slq[2] << ", "
+                          << slq[3] << "]" << std::endl;
             if (shifted) {
                 const std::vector<cgx_result> &sr = solver.shift_results();
                 for (size_t j = 0; j < sr.size(); ++j)

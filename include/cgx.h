@@ -381,6 +381,47 @@ cgx_status  cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long l
 #define CGX_MAX_SHIFTS 16
 cgx_status  cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res);
 
+/* ---- Lanczos quadrature: log det A, tr(A^-1) and spectrum estimates of the current matrix ---- */
+/* The symmetric Lanczos three-term recurrence from nvec start vectors at once, one pass over A per step for all of them
+ * (csrc/cgx_lanczos.hip; the mat-vec is cgx_solve_multi's plain multi-vector K1).  Per start vector j:
+ *   v_0 = V0_j / ||V0_j||, v_-1 = 0;  step t: y = A v_t, alpha_t = v_t . y, w = y - alpha_t v_t - beta_(t-1) v_(t-1), beta_t = ||w||;
+ *   beta_t <= 2^-36 max_(s<=t) |alpha_s|: the column has reached an invariant subspace and is frozen with m_j = t + 1 steps (the
+ *   others go on); else v_(t+1) = w / beta_t.
+ * There is NO reorthogonalisation: the coefficients are those of the plain recurrence in floating point, which is what Gauss
+ * quadrature needs (the Ritz values may repeat once they have converged; the rule stays accurate).
+ * V0: host array, one start vector per ROW, V0[j*ldv + i], i < n.  alpha, beta: nvec rows of `steps` doubles (alpha[j*steps + t]);
+ * beta[.. + t] = beta_t, the last one included; entries at t >= steps_done[j] are 0; steps_done[j] = m_j.  Column j's result depends
+ * on (A, V0_j, steps, the kernel width of nvec: 1, 2, 4, 8 or 16) only: permuting the columns permutes the results bit for bit.
+ * One GPU (CGX_COMM_SELF) and dense storage only, else CGX_ERR_UNSUPPORTED; a preconditioner that is set is CGX_ERR_UNSUPPORTED too
+ * (the call would ignore it).  CGX_ERR_BAD_ARG: a null pointer, no matrix, nvec outside 1 .. CGX_MAX_RHS, steps < 1, steps > n or
+ * steps > CGX_MAX_LANCZOS_STEPS, ldv < n, a start vector of norm 0 or not finite (its column in cgx_last_error).  A failed call
+ * leaves the context usable; the single path's plan and state are left as they were. */
+#define CGX_MAX_LANCZOS_STEPS 1024
+#define CGX_MAX_PROBES 256
+enum { CGX_SLQ_LOG = 0, CGX_SLQ_INV = 1 };
+cgx_status  cgx_lanczos(cgx_ctx *ctx, int nvec, int steps, const double *V0, long ldv, double *alpha, double *beta, int *steps_done);
+
+/* Stochastic Lanczos quadrature: tr f(A) ~ (1/nprobe) sum_j ||z_j||^2 sum_i tau_i^2 f(theta_i) with (theta, tau) the Ritz values
+ * and first eigenvector components of probe j's Jacobi matrix T_j (cgx_tridiag_quadrature), f = log (CGX_SLQ_LOG: log det A) or
+ * 1/x (CGX_SLQ_INV: tr A^-1).  Z = NULL: Rademacher probes made by the library, element i of probe j = -1 if the top bit of
+ * hash_mix64(hash_mix64(seed) ^ (j << 32 | i)) is set, else +1 (hash_mix64: the splitmix64 finaliser, z += 0x9E3779B97F4A7C15;
+ * z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31); else nprobe caller's vectors, one per
+ * row (Z[j*ldz + i]; seed is not read).  The probes run through cgx_lanczos's recurrence in batches of 8 (the last batch may be
+ * smaller): the value of probe j depends on (A, z_j, steps, the size of its batch) only, so permuting the probes within a batch
+ * permutes per_probe bit for bit.  *estimate = the mean over the probes, *std_error = their sample standard deviation /
+ * sqrt(nprobe) (0 for one probe); per_probe (nprobe doubles) and ritz (2 doubles: the smallest / largest Ritz value over all
+ * probes) may be NULL.  Scope and refusals as cgx_lanczos (ldz is read only with Z); also CGX_ERR_BAD_ARG: nprobe outside
+ * 1 .. CGX_MAX_PROBES, an unknown fn, and under either fn a Ritz value <= 0: "matrix is not positive definite", the value in
+ * cgx_last_error. */
+cgx_status  cgx_trace_slq(cgx_ctx *ctx, int fn, int nprobe, int steps, unsigned long long seed, const double *Z, long ldz,
+                          double *estimate, double *std_error, double *per_probe, double *ritz);
+
+/* HOST ONLY, no context: nodes and weights of the m-point Gauss rule of the Jacobi matrix with diagonal alpha[0..m) and
+ * off-diagonal beta[0..m-1) (beta may be NULL for m = 1): theta ascending, weight_i = (first component of eigenvector i)^2.
+ * Implicit symmetric QL on the first row of the eigenvector matrix alone, O(m^2), no LAPACK.  CGX_ERR_BAD_ARG: m < 1, a null
+ * pointer, an entry that is not finite.  CGX_ERR_UNSUPPORTED: a value did not converge within 60 sweeps (not seen so far). */
+cgx_status  cgx_tridiag_quadrature(int m, const double *alpha, const double *beta, double *theta, double *weight);
+
 /* ---- kernel probes (parity tests of the individual hot ops through the C ABI) ------------- */
 /* Ap = A_shard * p  (K1; cblas_dgemv at cg.cc:101-102) for every local shard; y receives the n
  * results in global row order (LOOPBACK/SELF) or this rank's rows at their global offset (RCCL);
