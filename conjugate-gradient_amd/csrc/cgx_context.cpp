@@ -119,6 +119,9 @@ void free_problem(cgx_ctx *ctx)
     (void)hipFree(ctx->lanczos);
     ctx->lanczos = nullptr;
     ctx->lanczos_bytes = 0;
+    (void)hipFree(ctx->lanczos_pc);
+    ctx->lanczos_pc = nullptr;
+    ctx->lanczos_pc_bytes = 0;
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     ctx->h_stage = nullptr;
     ctx->d_gathered_ptrs = nullptr;

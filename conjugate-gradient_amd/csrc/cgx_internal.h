@@ -195,6 +195,10 @@ struct cgx_ctx {
     // blocks of the recurrence, Y, the partials, the alpha / beta histories and the scalars; made on first use, freed with the problem
     double *lanczos = nullptr;
     size_t lanczos_bytes = 0;
+    // ... and the preconditioned recurrence's own block (cgx_lanczos_pc, cgx_trace_slq_pc, cgx_lanczos_pc_host.cpp): w, v_prev, u, Y,
+    // the partials (K1m's, two w.u sets, those of L^T w), the histories and the scalars; made on first use, freed with the problem
+    double *lanczos_pc = nullptr;
+    size_t lanczos_pc_bytes = 0;
 
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 

@@ -624,4 +624,43 @@ hipError_t launch_lanczos_step(const LanczosArgs &a, hipStream_t s);
 // Behind the last step: beta_(steps-1) and m = steps for the columns still running.
 hipError_t launch_lanczos_close(int n, int nvec, int steps, const double *ww, LanczosScalars *ls, double *beta, hipStream_t s);
 
+// ---- the same with a preconditioner (cgx_lanczos_pc, cgx_trace_slq_pc; cgx_lanczos_pc.hip) ----------------
+// Per column w (the side of M), u = M^-1 w and v_prev; K1m runs on the not yet normalised u.  LanczosScalars keeps its meaning with
+// z2 = eta0^2 = w_0 . M^-1 w_0.  dinv != nullptr: point Jacobi, one launch per step (grid tiles x nvec); else the pivoted-Cholesky
+// factor, two launches of one workgroup per 256-row tile that serve every live column (the step, then the apply).
+struct LanczosPcArgs {
+    int n, nvec;
+    long lda;
+    double *w;                 // in: the unnormalised w_t;   out: v_t = w_t / beta_(t-1)
+    double *vprev;             // in: v_(t-1);                out: the unnormalised w_(t+1)
+    double *u;                 // in (K1m's operand): u_t;    out: u_(t+1) = M^-1 w_(t+1)
+    const double *Y;           // K1m's A u_t
+    const double *k1p;         // K1m's u_t . A u_t partials, g1 per column
+    int g1;
+    const double *wu_in;       // w_t . u_t partials, multi_update_grid(n) per column
+    double *wu_out;            // w_(t+1) . u_(t+1) partials
+    LanczosScalars *ls;
+    double *alpha, *beta;      // the histories: kMaxRhs rows of kMaxLanczosSteps
+    int t;
+    const double *dinv;        // point Jacobi: the inverse diagonal (lda doubles); nullptr = pivoted Cholesky:
+    const double *L;           //   rank x lda, column-major at the matrix pitch
+    int rank;
+    const double *Cinv;        //   (delta I + L^T L)^-1 at pitch kLrLd
+    const LrHead *head;        //   delta
+    double *tpart;             //   kMaxRhs x lr_grid(n) x kLrLd: per column and tile the partials of t_j = L^T w_j
+};
+// The set-up from w = V0 as it is: u_0 = M^-1 w_0, v_-1 = 0, the w_0 . u_0 partials into wu_out, and per column eta0^2 folded in the
+// steps' order and the scalars reset; a column whose eta0^2 is 0, negative or not finite is marked bad and never runs.
+hipError_t launch_lanczos_pc_init(const LanczosPcArgs &a, hipStream_t s);
+// Step t behind K1m: beta_(t-1) and the breakdown test, alpha_t, v_t over w, w_(t+1) over v_(t-1), u_(t+1), the next partials.
+hipError_t launch_lanczos_pc_step(const LanczosPcArgs &a, hipStream_t s);
+// Behind the last step: beta_(steps-1) and m = steps for the columns still running.
+hipError_t launch_lanczos_pc_close(int n, int nvec, int steps, const double *wu, LanczosScalars *ls, double *beta, hipStream_t s);
+// nprobe probes (probe0, probe0 + 1, ... of the seed) into Z (column j at + j * lda): kind 0 = cgx_trace_slq's Rademacher signs
+// (covariance I); kLpcJacobi: sign_i sqrt(A_ii); kLpcLowrank: L g + sqrt(delta) sign with g_c the sign of element n + c
+// (covariance M = the preconditioner, exactly).
+constexpr int kLpcJacobi = 1, kLpcLowrank = 2;
+hipError_t launch_lanczos_pc_probes(int n, long lda, int nprobe, int kind, unsigned long long seed_mixed, int probe0, const double *A,
+                                    const double *L, int rank, const LrHead *head, double *Z, hipStream_t s);
+
 }  // namespace cgx

@@ -26,6 +26,8 @@
 // Lanczos quadrature with P Rademacher probes (1 ... 256) of M Lanczos steps each (default 100, at most min(n, 1024)).  The timing
 // line in OUTFILE is written as ever; one line with the estimate, its standard error and the extreme Ritz values follows on stdout.
 // One GPU, dense storage, no preconditioner, not with --shifts; the matrix must be symmetric positive definite.
+// `--logdet-pc P[,M]` is the same through the preconditioner that --jacobi or --pivchol K sets (cgx_trace_slq_pc): log det M plus the
+// quadrature of M^-1/2 A M^-1/2 with probes of covariance M, M steps each (default 30); the line also prints log det M.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -163,6 +165,9 @@ int usage(const char *prog)
               << "         --logdet P[,M]           opt-in, not in the reference: estimate log det A instead of solving, by stochastic\n"
               << "                                  Lanczos quadrature with P probes (1 ... 256) of M steps (default 100); one GPU,\n"
               << "                                  dense storage, no preconditioner, not with --shifts; prints one line\n"
+              << "         --logdet-pc P[,M]        opt-in, not in the reference: --logdet through the preconditioner (needs --jacobi or\n"
+              << "                                  --pivchol K): log det M plus P probes (1 ... 256) of M steps (default 30) on\n"
+              << "                                  M^-1/2 A M^-1/2; not with --shifts; prints --logdet's line plus log det M\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -188,6 +193,7 @@ int main(int argc, char **argv)
     std::vector<double> shifts;
     bool shifted = false;
     int logdet_probes = 0, logdet_steps = 100;   // --logdet P[,M] (0 probes: off)
+    int logdet_pc_probes = 0, logdet_pc_steps = 30;   // --logdet-pc P[,M] (0 probes: off)
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -244,6 +250,18 @@ int main(int argc, char **argv)
                 return usage(argv[0]);
             }
         }
+        else if (a == "--logdet-pc" && i + 1 < argc) {
+            const std::string arg(argv[++i]);
+            const size_t comma = arg.find(',');
+            const bool ok = parse_int(arg.substr(0, comma), &logdet_pc_probes) &&
+                            (comma == std::string::npos || parse_int(arg.substr(comma + 1), &logdet_pc_steps));
+            if (!ok || logdet_pc_probes < 1 || logdet_pc_probes > CGX_MAX_PROBES || logdet_pc_steps < 1 ||
+                logdet_pc_steps > CGX_MAX_LANCZOS_STEPS) {
+                std::cerr << argv[0] << ": --logdet-pc takes P[,M] with 1 <= P <= " << CGX_MAX_PROBES << " probes and 1 <= M <= "
+                          << CGX_MAX_LANCZOS_STEPS << " steps, not '" << arg << "'\n";
+                return usage(argv[0]);
+            }
+        }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -272,6 +290,14 @@ int main(int argc, char **argv)
     }
     if (logdet_probes && (shifted || jacobi || pivchol)) {
         std::cerr << argv[0] << ": --logdet runs without a preconditioner and not together with --shifts\n";
+        return usage(argv[0]);
+    }
+    if (logdet_pc_probes && (shifted || logdet_probes)) {
+        std::cerr << argv[0] << ": --logdet-pc runs not together with --shifts or --logdet\n";
+        return usage(argv[0]);
+    }
+    if (logdet_pc_probes && !(jacobi || pivchol)) {
+        std::cerr << argv[0] << ": --logdet-pc needs a preconditioner (--jacobi or --pivchol K); without one --logdet is the call\n";
         return usage(argv[0]);
     }
     if (ngpu < 1) ngpu = 1;
@@ -502,10 +528,16 @@ int main(int argc, char **argv)
         auto t1 = clk::now();                                // only solve() is timed, cg_main.cc:53-55
         std::vector<double> x_shifted;                       // --shifts: one solution per shift
         double slq[4] = {0, 0, 0, 0};                        // --logdet: estimate, standard error, smallest / largest Ritz value
+        double slq_pc = 0;                                   // --logdet-pc: log det of the preconditioner
         if (logdet_probes) {
             if (cgx_trace_slq(solver.context(), CGX_SLQ_LOG, logdet_probes, logdet_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
                               &slq[2]) != CGX_OK)
                 throw std::runtime_error(std::string("--logdet: ") + cgx_last_error(solver.context()));
+        }
+        else if (logdet_pc_probes) {
+            if (cgx_trace_slq_pc(solver.context(), CGX_SLQ_LOG, logdet_pc_probes, logdet_pc_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
+                                 &slq[2], &slq_pc) != CGX_OK)
+                throw std::runtime_error(std::string("--logdet-pc: ") + cgx_last_error(solver.context()));
         }
         else if (shifted) solver.solve_shifted(shifts, x_shifted);
         else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
@@ -524,6 +556,11 @@ int main(int argc, char **argv)
                 std::cout << "\t[LOGDET] probes = " << logdet_probes << ", steps = " << logdet_steps << ", log det A = " << std::setprecision(12)
                           << slq[0] << ", standard error = " << std::setprecision(6) << slq[1] << ", Ritz values in [" << slq[2] << ", "
                           << slq[3] << "]" << std::endl;
+            if (logdet_pc_probes)
+                std::cout << "\t[LOGDET] probes = " << logdet_pc_probes << ", steps = " << logdet_pc_steps << ", log det A = "
+                          << std::setprecision(12) << slq[0] << ", standard error = " << std::setprecision(6) << slq[1]
+                          << ", Ritz values in [" << slq[2] << ", " << slq[3] << "], log det M = " << std::setprecision(12) << slq_pc
+                          << std::setprecision(6) << std::endl;
             if (shifted) {
                 const std::vector<cgx_result> &sr = solver.shift_results();
                 for (size_t j = 0; j < sr.size(); ++j)

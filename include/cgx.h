@@ -416,6 +416,47 @@ cgx_status  cgx_lanczos(cgx_ctx *ctx, int nvec, int steps, const double *V0, lon
 cgx_status  cgx_trace_slq(cgx_ctx *ctx, int fn, int nprobe, int steps, unsigned long long seed, const double *Z, long ldz,
                           double *estimate, double *std_error, double *per_probe, double *ritz);
 
+/* ---- preconditioned Lanczos quadrature ---- */
+/* cgx_lanczos with the context's preconditioner M (M = diag A for CGX_PRECOND_JACOBI with block 1, M = L L^T + delta I for
+ * CGX_PRECOND_PIVCHOL), csrc/cgx_lanczos_pc.hip.  Per start vector j:
+ *   w_0 = V0_j, u_0 = M^-1 w_0, eta0^2 = w_0 . u_0, v_-1 = 0, beta_-1 := eta0;
+ *   step t: v_t = w_t / beta_(t-1), q_t = u_t / beta_(t-1), y = A q_t, alpha_t = q_t . y, w_(t+1) = y - alpha_t v_t - beta_(t-1) v_(t-1),
+ *   u_(t+1) = M^-1 w_(t+1), beta_t = sqrt(w_(t+1) . u_(t+1));  beta_t^2 <= 0 or beta_t <= 2^-36 max_(s<=t) |alpha_s|: frozen with
+ *   m_j = t + 1.
+ * (alpha, beta) are the Jacobi matrix of M^-1/2 A M^-1/2 from the start vector M^-1/2 V0_j, so that V0_j^T M^-1/2 f(M^-1/2 A M^-1/2)
+ * M^-1/2 V0_j ~ eta2[j] sum_i tau_i^2 f(theta_i) (cgx_tridiag_quadrature).  No reorthogonalisation.  Arguments, layout and argument
+ * errors as cgx_lanczos; eta2: nvec doubles, eta0^2 as the device summed it; a start vector whose eta0^2 is 0, negative or not
+ * finite is CGX_ERR_BAD_ARG with its column in cgx_last_error.  Column j's result depends on (A, V0_j, steps, the kernel width of
+ * nvec, the preconditioner's settings) only.  CGX_PRECOND_NONE: cgx_lanczos itself, bit for bit, eta2[j] = ||V0_j||^2.
+ * Scope and refusals are cgx_solve_multi_pc's, with its statuses, messages and order: one GPU (CGX_COMM_SELF) and dense storage,
+ * else CGX_ERR_UNSUPPORTED; block Jacobi, gemv_variant 40000 / 50000 and a K1 shape with split columns: CGX_ERR_UNSUPPORTED; rank >
+ * n, a matrix that is not positive definite: CGX_ERR_BAD_ARG.  The inverse diagonal / the factor is the single path's, made once
+ * per matrix (rank, shift) by whichever call comes first.  A failed call leaves the context usable; the single path's plan and
+ * state are left as they were.  cgx_lanczos and cgx_trace_slq keep refusing a preconditioner. */
+cgx_status  cgx_lanczos_pc(cgx_ctx *ctx, int nvec, int steps, const double *V0, long ldv, double *alpha, double *beta, int *steps_done,
+                           double *eta2);
+/* log det M of the preconditioner that is set (made here if no call has made it yet): CGX_PRECOND_JACOBI the sum of log A_ii in
+ * ascending order; CGX_PRECOND_PIVCHOL (n - rank) log delta + log det(delta I + L^T L), the second term from a host Cholesky
+ * factorisation of the device's (delta I + L^T L)^-1; CGX_PRECOND_NONE 0.  Scope and refusals as cgx_lanczos_pc. */
+cgx_status  cgx_precond_logdet(cgx_ctx *ctx, double *logdet);
+/* The nprobe probes that cgx_trace_slq_pc makes itself (Z = NULL) for fn, seed and the preconditioner that is set, one per row
+ * (Z[j*ldz + i]).  With s_(j,i) cgx_trace_slq's Rademacher sign of element i of probe j: CGX_SLQ_INV, or CGX_PRECOND_NONE: z = s_j
+ * (covariance I).  CGX_SLQ_LOG: covariance M exactly -- Jacobi z_i = s_(j,i) sqrt(A_ii); pivoted Cholesky z = L g + sqrt(delta) s_j
+ * with g_c = s_(j, n + c), per row one fma chain over c = 0 .. rank-1 from +0.0, then fma(sqrt(delta), s_(j,i), chain). */
+cgx_status  cgx_slq_probes(cgx_ctx *ctx, int fn, int nprobe, unsigned long long seed, double *Z, long ldz);
+/* cgx_trace_slq through cgx_lanczos_pc, in batches of 8 probes.
+ * CGX_SLQ_LOG: log det A = log det M + tr log(M^-1/2 A M^-1/2); the probes must have covariance M: the library's (Z = NULL, see
+ * cgx_slq_probes) or the caller's -- THE CALLER ANSWERS FOR THE COVARIANCE OF ITS OWN PROBES, nothing checks it, and with another
+ * covariance the estimate is that of another quantity.  per_probe[j] = eta0^2 sum_i tau_i^2 log theta_i, *estimate = log det M +
+ * their mean, *std_error that of the per-probe values, *logdet_precond (may be NULL) = log det M (cgx_precond_logdet).
+ * CGX_SLQ_INV: the probes have covariance I (Z = NULL: cgx_trace_slq's Rademacher vectors, bit for bit); per_probe[j] = eta0^2
+ * sum_i tau_i^2 / theta_i = z_j^T A^-1 z_j, *estimate their mean, *logdet_precond = 0.  The preconditioner cuts the steps needed.
+ * ritz: the extreme Ritz values of M^-1/2 A M^-1/2.  CGX_PRECOND_NONE: cgx_trace_slq itself, bit for bit, *logdet_precond = 0.
+ * Scope and refusals as cgx_lanczos_pc, argument errors as cgx_trace_slq; a Ritz value <= 0: CGX_ERR_BAD_ARG "matrix is not
+ * positive definite", the value in cgx_last_error. */
+cgx_status  cgx_trace_slq_pc(cgx_ctx *ctx, int fn, int nprobe, int steps, unsigned long long seed, const double *Z, long ldz,
+                             double *estimate, double *std_error, double *per_probe, double *ritz, double *logdet_precond);
+
 /* HOST ONLY, no context: nodes and weights of the m-point Gauss rule of the Jacobi matrix with diagonal alpha[0..m) and
  * off-diagonal beta[0..m-1) (beta may be NULL for m = 1): theta ascending, weight_i = (first component of eigenvector i)^2.
  * Implicit symmetric QL on the first row of the eigenvector matrix alone, O(m^2), no LAPACK.  CGX_ERR_BAD_ARG: m < 1, a null
