@@ -42,11 +42,13 @@ EXPORTS = [
     "cgx_solve_multi_pc", "cgx_probe_multi_pc_apply",
     "cgx_lanczos", "cgx_trace_slq", "cgx_tridiag_quadrature",
     "cgx_lanczos_pc", "cgx_precond_logdet", "cgx_slq_probes", "cgx_trace_slq_pc",
+    "cgx_tridiag_function", "cgx_apply_function", "cgx_probe_funm_combine",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 MAX_LANCZOS_STEPS = 1024   # CGX_MAX_LANCZOS_STEPS
 MAX_PROBES = 256           # CGX_MAX_PROBES
 SLQ_LOG, SLQ_INV = 0, 1    # cgx_trace_slq's fn
+FN_SQRT, FN_INVSQRT, FN_INV, FN_LOG, FN_EXP = 0, 1, 2, 3, 4   # CGX_FN_*: cgx_apply_function's and cgx_tridiag_function's fn
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 PRECOND_PIVCHOL = 2                   # the pivoted-Cholesky low-rank factor: one GPU, dense storage
@@ -173,6 +175,9 @@ def lib():
         L.cgx_precond_logdet.argtypes = [vp, dp]
         L.cgx_slq_probes.argtypes = [vp, C.c_int, C.c_int, C.c_ulonglong, dp, C.c_long]
         L.cgx_trace_slq_pc.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, dp, C.c_long, dp, dp, dp, dp, dp]
+        L.cgx_tridiag_function.argtypes = [C.c_int, dp, dp, C.c_int, C.c_double, dp, dp]
+        L.cgx_apply_function.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, dp, C.c_long, dp, C.c_long, ip, dp, dp]
+        L.cgx_probe_funm_combine.argtypes = [vp, C.c_int, C.c_int, ip, dp, C.c_long, dp, dp, C.c_long]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
         L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
@@ -214,6 +219,24 @@ def comm_unique_id():
     if st:
         raise CgxError(st, lib().cgx_last_error(None).decode(errors="replace"))
     return bytes(buf)
+
+
+def tridiag_function(alpha, beta, fn, param=0.0):
+    """Host only: f(T) e_1 for the Jacobi matrix with diagonal alpha (m entries) and off-diagonal beta (at least m - 1 entries, the
+    rest is not read), f one of FN_SQRT, FN_INVSQRT, FN_INV, FN_LOG, FN_EXP (exp(-param theta)).  Returns (coef, theta_min,
+    theta_max) (include/cgx.h cgx_tridiag_function)."""
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    m = alpha.size
+    if beta.size < m - 1:
+        raise ValueError("beta must have at least m - 1 entries")
+    coef = np.zeros(max(m, 1), dtype=np.float64)
+    mm = np.full(2, np.nan)
+    st = lib().cgx_tridiag_function(int(m), _dp(alpha), _dp(beta) if beta.size else None, int(fn), float(param), _dp(coef), _dp(mm))
+    if st:
+        raise CgxError(st, "cgx_tridiag_function: %s (eigenvalues of T in [%r, %r])"
+                       % (lib().cgx_status_string(st).decode(errors="replace"), mm[0], mm[1]))
+    return coef[:m], mm[0], mm[1]
 
 
 def parse_matrix_market(path, threads=0):
@@ -567,6 +590,34 @@ class CGSolver:
         self._check(lib().cgx_lanczos_pc(self._h, int(k), steps, _dp(V0), int(V0.shape[1]), _dp(alpha), _dp(beta),
                                          done.ctypes.data_as(C.POINTER(C.c_int)), _dp(eta2)))
         return alpha[:k, :steps], beta[:k, :steps], done[:k], eta2[:k]
+
+    def apply_function(self, B, fn, steps, param=0.0):
+        """B: float64 array (k, n), one vector per row (k <= MAX_RHS); fn one of FN_SQRT, FN_INVSQRT, FN_INV, FN_LOG, FN_EXP
+        (exp(-param A)).  Returns (X, info): X[j] ~ f(A) B[j] from `steps` Lanczos steps on the current matrix, one pass over A per
+        step for all vectors (include/cgx.h cgx_apply_function); info = dict(steps_done, change, coef): the steps every column
+        made, the convergence indicator and the coefficients of the Lanczos vectors, shape (k, steps)."""
+        B = np.ascontiguousarray(B, dtype=np.float64)
+        assert B.ndim == 2 and B.shape[1] == self.n(), B.shape
+        k, steps = B.shape[0], int(steps)
+        X = np.zeros((max(k, 1), B.shape[1]), dtype=np.float64)
+        coef = np.zeros((max(k, 1), max(steps, 1)), dtype=np.float64)
+        change = np.zeros(max(k, 1), dtype=np.float64)
+        done = np.zeros(max(k, 1), dtype=np.int32)
+        self._check(lib().cgx_apply_function(self._h, int(fn), float(param), int(k), steps, _dp(B), int(B.shape[1]), _dp(X),
+                                             int(X.shape[1]), done.ctypes.data_as(C.POINTER(C.c_int)), _dp(change), _dp(coef)))
+        return X[:k], {"steps_done": done[:k], "change": change[:k], "coef": coef[:k, :steps]}
+
+    def _probe_funm_combine(self, Q, Cf, m):
+        """Test hook: Q float64 (steps, k, n), Cf (k, steps), m k step counts; returns X (k, n) with X[j] = sum over t < m[j] of
+        Cf[j, t] Q[t, j] from the combine kernel of apply_function."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        Cf = np.ascontiguousarray(Cf, dtype=np.float64)
+        m = np.ascontiguousarray(m, dtype=np.int32)
+        assert Q.ndim == 3 and Q.shape[2] == self.n() and Cf.shape == (Q.shape[1], Q.shape[0]) and m.shape == (Q.shape[1],)
+        X = np.zeros((Q.shape[1], Q.shape[2]), dtype=np.float64)
+        self._check(lib().cgx_probe_funm_combine(self._h, int(Q.shape[1]), int(Q.shape[0]), m.ctypes.data_as(C.POINTER(C.c_int)), _dp(Q),
+                                                 int(Q.shape[2]), _dp(Cf), _dp(X), int(X.shape[1])))
+        return X
 
     def precond_logdet(self):
         """log det M of the preconditioner that is set (0.0 with none); makes the preconditioner if no call has made it yet."""

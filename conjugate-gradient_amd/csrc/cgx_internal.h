@@ -199,6 +199,11 @@ struct cgx_ctx {
     // the partials (K1m's, two w.u sets, those of L^T w), the histories and the scalars; made on first use, freed with the problem
     double *lanczos_pc = nullptr;
     size_t lanczos_pc_bytes = 0;
+    // matrix functions (cgx_apply_function, cgx_funm_host.cpp): the coefficient table, the step counts, the result block and the kept
+    // Lanczos basis (steps x nvec x lda doubles of the call); made on first use, made again when a call needs more, freed with
+    // the problem
+    double *funm = nullptr;
+    size_t funm_bytes = 0;
 
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 
@@ -345,6 +350,14 @@ double one_gpu_gemv_bytes(const cgx_ctx *ctx);             // algorithmic bytes 
 cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn);
 // A side block of the context (cgx_ctx::multi, cgx_ctx::shift): allocated and zeroed on first use, freed again if that fails.
 cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes);
+
+// cgx_lanczos_host.cpp: what cgx_apply_function (cgx_funm_host.cpp) shares with cgx_lanczos and the Gauss rule
+cgx_status check_lanczos(cgx_ctx *ctx, const char *name, int steps);
+cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, const double *V0, long ldv, int col0, double *alpha,
+                       double *beta, int *m, double *z2, double *basis = nullptr);
+bool funm_args_ok(int fn, double param);   // a known CGX_FN_*, and for CGX_FN_EXP a finite param >= 0
+enum class TridiagFn { ok, no_convergence, domain };
+TridiagFn tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *minmax, double *bad);
 
 // Lays a side block out in 128-byte aligned pieces; base == nullptr only measures (bytes()).
 struct Carver {

@@ -663,4 +663,17 @@ constexpr int kLpcJacobi = 1, kLpcLowrank = 2;
 hipError_t launch_lanczos_pc_probes(int n, long lda, int nprobe, int kind, unsigned long long seed_mixed, int probe0, const double *A,
                                     const double *L, int rank, const LrHead *head, double *Z, hipStream_t s);
 
+// ---- a matrix function applied to vectors (cgx_apply_function; cgx_funm.hip) -------------------------------
+// X_j[i] = sum over t < m[j] of C[j * steps + t] * Q[(t * nvec + j) * lda + i], one fma chain per element in ascending t from +0.0.
+struct FunmArgs {
+    int n, nvec, steps;
+    long lda;
+    const double *Q;           // the kept Lanczos basis: steps slots of nvec x lda doubles; slots at t >= m[j] are never read
+    const double *C;           // nvec rows of `steps` coefficients
+    const int *m;              // nvec step counts, 0 .. steps
+    double *X;                 // nvec x ldx
+    long ldx;
+};
+hipError_t launch_funm_combine(const FunmArgs &a, hipStream_t s);
+
 }  // namespace cgx

@@ -1,5 +1,6 @@
-// cgx_lanczos_host.cpp -- cgx_lanczos, cgx_trace_slq and cgx_tridiag_quadrature: the host side of the multi-vector Lanczos
-// recurrence (cgx_lanczos.hip) and stochastic Lanczos quadrature on top of it.
+// cgx_lanczos_host.cpp -- cgx_lanczos, cgx_trace_slq, cgx_tridiag_quadrature and cgx_tridiag_function: the host side of the
+// multi-vector Lanczos recurrence (cgx_lanczos.hip), stochastic Lanczos quadrature on top of it and the
+// host-only functions of a Jacobi matrix (f(T) e_1 for cgx_apply_function).
 //
 // One GPU, dense storage.  The blocks live in ONE device allocation of the context (cgx_ctx::lanczos), apart from the single
 // path's buffers and from the multi blocks, made on the first call of a problem and freed with it.  A step is two launches -- the
@@ -43,8 +44,11 @@ size_t lanczos_layout(const cgx_ctx *ctx, double *base, LanczosView *v)
     return c.bytes();
 }
 
-// The checks both entry points make, in this order: context, problem, transport, storage, preconditioner, steps.
-cgx_status check_lanczos(cgx_ctx *ctx, const char *name, int steps)
+}  // namespace
+
+// The checks every entry point on the plain recurrence makes, in this order: context, problem, transport, storage, preconditioner,
+// steps.
+cgx_status cgxi::check_lanczos(cgx_ctx *ctx, const char *name, int steps)
 {
     const std::string fn(name);
     CGX_TRY(check_one_gpu_call(ctx, fn));
@@ -58,9 +62,10 @@ cgx_status check_lanczos(cgx_ctx *ctx, const char *name, int steps)
 
 // THE recurrence: nvec start vectors (one per row of V0, pitch ldv) through `steps` steps.  alpha, beta: nvec rows of `steps`
 // doubles, zero at t >= m[j]; z2[j] = ||V0_j||^2 as the device summed it.  col0: the number of row 0 in the caller's own count,
-// for the message about a bad start vector.
-cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, const double *V0, long ldv, int col0, double *alpha,
-                       double *beta, int *m, double *z2)
+// for the message about a bad start vector.  basis != nullptr (cgx_apply_function): behind step t the block that now holds the
+// normalised v_t is copied into slot t of the basis, nvec * lda doubles each; with a null pointer no such call is made.
+cgx_status cgxi::lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, const double *V0, long ldv, int col0, double *alpha,
+                             double *beta, int *m, double *z2, double *basis)
 {
     LanczosView v;
     CGX_TRY(ensure_side_block(ctx, &ctx->lanczos, &ctx->lanczos_bytes, lanczos_layout(ctx, nullptr, &v)));
@@ -100,6 +105,8 @@ cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, cons
         a.beta = v.beta;
         a.t = t;
         HIP_TRY(ctx, cgx::launch_lanczos_step(a, st));
+        if (basis)
+            HIP_TRY(ctx, hipMemcpyAsync(basis + (size_t)t * nvec * lda, w, (size_t)nvec * lda * sizeof(double), hipMemcpyDeviceToDevice, st));
     }
     HIP_TRY(ctx, cgx::launch_lanczos_close(n, nvec, steps, v.wwp[steps & 1], v.ls, v.beta, st));
     cgx::LanczosScalars hs;
@@ -120,12 +127,21 @@ cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, cons
     return CGX_OK;
 }
 
+namespace {
+
 // sqrt(a^2 + b^2) without overflow (the QL sweep's plane rotations)
 double pythag(double a, double b) { return std::hypot(a, b); }
 
 // Implicit symmetric QL with Wilkinson's shift on (d, e), carrying the FIRST ROW z of the eigenvector matrix along: the rotations
 // of a sweep are applied to z alone, so the work is O(m^2) and nothing m x m is held.  e[i] couples i and i + 1; e[m-1] is work space.
-bool ql_first_row(int m, double *d, double *e, double *z)
+// rec != nullptr: every plane rotation applied to z is appended, in the order applied (about 1.1 m^2 of them); the arithmetic of
+// the sweep is the same with and without.
+struct Rotation {
+    int i;
+    double c, s;
+};
+
+bool ql_first_row(int m, double *d, double *e, double *z, std::vector<Rotation> *rec = nullptr)
 {
     for (int l = 0; l < m; ++l) {
         int iter = 0, mm;
@@ -161,6 +177,7 @@ bool ql_first_row(int m, double *d, double *e, double *z)
                     f = z[i + 1];
                     z[i + 1] = s * z[i] + c * f;
                     z[i] = c * z[i] - s * f;
+                    if (rec) rec->push_back(Rotation{i, c, s});
                 }
                 if (r == 0.0 && i >= l) continue;
                 d[l] -= p;
@@ -199,9 +216,80 @@ double rademacher(unsigned long long seed_mixed, unsigned long long j, unsigned 
     return (cgx::hash_mix64(seed_mixed ^ ((j << 32) | i)) >> 63) ? -1.0 : 1.0;
 }
 
+bool funm_in_domain(int fn, double theta)
+{
+    return fn == CGX_FN_EXP || (fn == CGX_FN_SQRT ? theta >= 0.0 : theta > 0.0);
+}
+
+double funm_value(int fn, double param, double theta)
+{
+    switch (fn) {
+    case CGX_FN_SQRT: return std::sqrt(theta);
+    case CGX_FN_INVSQRT: return 1.0 / std::sqrt(theta);
+    case CGX_FN_INV: return 1.0 / theta;
+    case CGX_FN_LOG: return std::log(theta);
+    default: return std::exp(-param * theta);
+    }
+}
+
 }  // namespace
 
+bool cgxi::funm_args_ok(int fn, double param)
+{
+    if (fn < CGX_FN_SQRT || fn > CGX_FN_EXP) return false;
+    return fn != CGX_FN_EXP || (std::isfinite(param) && param >= 0.0);
+}
+
+// coef = f(T) e_1 for the m x m Jacobi matrix (alpha, beta), entries and arguments already checked.  The sweep of the Gauss rule runs
+// on (d, e, z) with every rotation recorded: with S their product in the order applied, T = S diag(d) S^T and z = S^T e_1, so
+// f(T) e_1 = S g with g_k = f(d_k) z_k, and S g is the recorded rotations applied to g from the last one back.  minmax (may be
+// null): the smallest and largest d, filled before the domain is looked at.  *bad: the smallest d when it lies outside the domain.
+cgxi::TridiagFn cgxi::tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *minmax,
+                                       double *bad)
+{
+    std::vector<double> work((size_t)3 * m, 0.0);
+    std::vector<Rotation> rot;
+    rot.reserve((size_t)m * m + (size_t)m * m / 4 + 64);
+    double *d = work.data(), *e = d + m, *z = e + m;
+    for (int i = 0; i < m; ++i) {
+        d[i] = alpha[i];
+        if (i + 1 < m) e[i] = beta[i];
+    }
+    z[0] = 1.0;
+    if (!ql_first_row(m, d, e, z, &rot)) return TridiagFn::no_convergence;
+    double lo = d[0], hi = d[0];
+    for (int i = 1; i < m; ++i) {
+        lo = std::min(lo, d[i]);
+        hi = std::max(hi, d[i]);
+    }
+    if (minmax) { minmax[0] = lo; minmax[1] = hi; }
+    if (!funm_in_domain(fn, lo)) {
+        if (bad) *bad = lo;
+        return TridiagFn::domain;
+    }
+    for (int i = 0; i < m; ++i) coef[i] = funm_value(fn, param, d[i]) * z[i];
+    for (size_t r = rot.size(); r-- > 0;) {
+        const Rotation &q = rot[r];
+        const double a = coef[q.i], b = coef[q.i + 1];
+        coef[q.i] = q.c * a + q.s * b;
+        coef[q.i + 1] = q.c * b - q.s * a;
+    }
+    return TridiagFn::ok;
+}
+
 extern "C" {
+
+cgx_status cgx_tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *theta_minmax)
+{
+    if (m < 1 || !alpha || !coef || (m > 1 && !beta) || !funm_args_ok(fn, param)) return CGX_ERR_BAD_ARG;
+    for (int i = 0; i < m; ++i)
+        if (!std::isfinite(alpha[i]) || (i + 1 < m && !std::isfinite(beta[i]))) return CGX_ERR_BAD_ARG;
+    switch (tridiag_function(m, alpha, beta, fn, param, coef, theta_minmax, nullptr)) {
+    case TridiagFn::ok: return CGX_OK;
+    case TridiagFn::domain: return CGX_ERR_BAD_ARG;        // an eigenvalue where f is not defined (theta_minmax is filled)
+    default: return CGX_ERR_UNSUPPORTED;                   // (no convergence in 60 sweeps per value)
+    }
+}
 
 cgx_status cgx_tridiag_quadrature(int m, const double *alpha, const double *beta, double *theta, double *weight)
 {

@@ -28,11 +28,16 @@
 // One GPU, dense storage, no preconditioner, not with --shifts; the matrix must be symmetric positive definite.
 // `--logdet-pc P[,M]` is the same through the preconditioner that --jacobi or --pivchol K sets (cgx_trace_slq_pc): log det M plus the
 // quadrature of M^-1/2 A M^-1/2 with probes of covariance M, M steps each (default 30); the line also prints log det M.
+// `--apply NAME[,M[,T]]` (NOT a reference mode) applies a function of the matrix to the source term instead of solving (include/cgx.h
+// cgx_apply_function): NAME = sqrt, invsqrt, inv, log or exp (exp(-T A)), M Lanczos steps (default 100, at most min(n, 1024)).  The
+// result goes where the solution goes; the timing line in OUTFILE is written as ever and one line with the steps made, the convergence
+// indicator and ||x|| follows on stdout.  One GPU, dense storage, no preconditioner, not with --shifts or --logdet.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
 
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdlib>
 #include <cstring>
@@ -168,6 +173,10 @@ int usage(const char *prog)
               << "         --logdet-pc P[,M]        opt-in, not in the reference: --logdet through the preconditioner (needs --jacobi or\n"
               << "                                  --pivchol K): log det M plus P probes (1 ... 256) of M steps (default 30) on\n"
               << "                                  M^-1/2 A M^-1/2; not with --shifts; prints --logdet's line plus log det M\n"
+              << "         --apply NAME[,M[,T]]     opt-in, not in the reference: x = f(A) b for the source term b instead of solving, by\n"
+              << "                                  M Lanczos steps (default 100); NAME = sqrt, invsqrt, inv, log or exp (exp(-T A),\n"
+              << "                                  T >= 0, default 1); one GPU, dense storage, no preconditioner, not with --shifts\n"
+              << "                                  or --logdet; prints one line\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -194,6 +203,9 @@ int main(int argc, char **argv)
     bool shifted = false;
     int logdet_probes = 0, logdet_steps = 100;   // --logdet P[,M] (0 probes: off)
     int logdet_pc_probes = 0, logdet_pc_steps = 30;   // --logdet-pc P[,M] (0 probes: off)
+    int apply_fn = -1, apply_steps = 100;        // --apply NAME[,M[,T]] (-1: off)
+    double apply_param = 1.0;
+    std::string apply_name;
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -262,6 +274,32 @@ int main(int argc, char **argv)
                 return usage(argv[0]);
             }
         }
+        else if (a == "--apply" && i + 1 < argc) {
+            const std::string arg(argv[++i]);
+            std::vector<std::string> part;
+            std::stringstream list(arg);
+            std::string item;
+            while (std::getline(list, item, ',')) part.push_back(item);
+            static const char *const names[] = {"sqrt", "invsqrt", "inv", "log", "exp"};   // CGX_FN_SQRT ... CGX_FN_EXP
+            bool ok = !part.empty() && part.size() <= 3 && arg.back() != ',';
+            if (ok) {
+                apply_name = part[0];
+                for (int f = 0; f < 5; ++f)
+                    if (part[0] == names[f]) apply_fn = f;
+                ok = apply_fn >= 0 && (part.size() == 3 ? apply_fn == CGX_FN_EXP : true);
+            }
+            if (ok && part.size() >= 2) ok = parse_int(part[1], &apply_steps);
+            if (ok && part.size() == 3) {
+                char *end = nullptr;
+                apply_param = strtod(part[2].c_str(), &end);
+                ok = !part[2].empty() && *end == '\0' && apply_param >= 0.0 && apply_param <= 1.7976931348623157e308;
+            }
+            if (!ok || apply_steps < 1 || apply_steps > CGX_MAX_LANCZOS_STEPS) {
+                std::cerr << argv[0] << ": --apply takes NAME[,M[,T]] with NAME one of sqrt, invsqrt, inv, log, exp, 1 <= M <= "
+                          << CGX_MAX_LANCZOS_STEPS << " steps and, for exp only, a finite T >= 0, not '" << arg << "'\n";
+                return usage(argv[0]);
+            }
+        }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -298,6 +336,10 @@ int main(int argc, char **argv)
     }
     if (logdet_pc_probes && !(jacobi || pivchol)) {
         std::cerr << argv[0] << ": --logdet-pc needs a preconditioner (--jacobi or --pivchol K); without one --logdet is the call\n";
+        return usage(argv[0]);
+    }
+    if (apply_fn >= 0 && (shifted || jacobi || pivchol || logdet_probes || logdet_pc_probes)) {
+        std::cerr << argv[0] << ": --apply runs without a preconditioner and not together with --shifts or --logdet\n";
         return usage(argv[0]);
     }
     if (ngpu < 1) ngpu = 1;
@@ -529,6 +571,8 @@ int main(int argc, char **argv)
         std::vector<double> x_shifted;                       // --shifts: one solution per shift
         double slq[4] = {0, 0, 0, 0};                        // --logdet: estimate, standard error, smallest / largest Ritz value
         double slq_pc = 0;                                   // --logdet-pc: log det of the preconditioner
+        int apply_done = 0;                                  // --apply: the steps made and the convergence indicator
+        double apply_change = 0;
         if (logdet_probes) {
             if (cgx_trace_slq(solver.context(), CGX_SLQ_LOG, logdet_probes, logdet_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
                               &slq[2]) != CGX_OK)
@@ -538,6 +582,13 @@ int main(int argc, char **argv)
             if (cgx_trace_slq_pc(solver.context(), CGX_SLQ_LOG, logdet_pc_probes, logdet_pc_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
                                  &slq[2], &slq_pc) != CGX_OK)
                 throw std::runtime_error(std::string("--logdet-pc: ") + cgx_last_error(solver.context()));
+        }
+        else if (apply_fn >= 0) {
+            std::vector<double> b(static_cast<size_t>(n), 0.);
+            if (cgx_probe_get_source_term(solver.context(), 0, b.data()) != CGX_OK ||
+                cgx_apply_function(solver.context(), apply_fn, apply_param, 1, apply_steps, b.data(), n, x_d.data(), n, &apply_done, &apply_change,
+                                   nullptr) != CGX_OK)
+                throw std::runtime_error(std::string("--apply: ") + cgx_last_error(solver.context()));
         }
         else if (shifted) solver.solve_shifted(shifts, x_shifted);
         else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
@@ -561,6 +612,13 @@ int main(int argc, char **argv)
                           << std::setprecision(12) << slq[0] << ", standard error = " << std::setprecision(6) << slq[1]
                           << ", Ritz values in [" << slq[2] << ", " << slq[3] << "], log det M = " << std::setprecision(12) << slq_pc
                           << std::setprecision(6) << std::endl;
+            if (apply_fn >= 0) {
+                double xx = 0.0;
+                for (double v : x_d) xx += v * v;
+                std::cout << "\t[APPLY] fn = " << apply_name << ", steps = " << apply_steps << ", steps_done = " << apply_done
+                          << ", change = " << std::setprecision(12) << apply_change << ", ||x|| = " << std::sqrt(xx) << std::setprecision(6)
+                          << std::endl;
+            }
             if (shifted) {
                 const std::vector<cgx_result> &sr = solver.shift_results();
                 for (size_t j = 0; j < sr.size(); ++j)

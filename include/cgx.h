@@ -463,6 +463,48 @@ cgx_status  cgx_trace_slq_pc(cgx_ctx *ctx, int fn, int nprobe, int steps, unsign
  * pointer, an entry that is not finite.  CGX_ERR_UNSUPPORTED: a value did not converge within 60 sweeps (not seen so far). */
 cgx_status  cgx_tridiag_quadrature(int m, const double *alpha, const double *beta, double *theta, double *weight);
 
+/* ---- a matrix function applied to vectors: A^(1/2) b, A^(-1/2) b, A^-1 b, log(A) b, exp(-tau A) b ---- */
+/* HOST ONLY, no context: coef[t] = (f(T) e_1)_t, t < m, for the Jacobi matrix T of cgx_tridiag_quadrature's arguments (beta may be
+ * NULL for m = 1) and f(theta) = sqrt(theta) (CGX_FN_SQRT), 1 / sqrt(theta) (CGX_FN_INVSQRT), 1 / theta (CGX_FN_INV), log(theta)
+ * (CGX_FN_LOG) or exp(-param theta) (CGX_FN_EXP; param is read for this function only and must be finite and >= 0).  The implicit
+ * QL sweep of cgx_tridiag_quadrature with every plane rotation of the first row recorded; f(T) e_1 is those rotations applied in
+ * reverse to f(d_k) z_k: O(m^2) time, about 1.1 m^2 recorded rotations of transient memory, no LAPACK.  theta_minmax (may be NULL)
+ * receives the smallest and largest eigenvalue of T, also when the call fails for the domain.  CGX_ERR_BAD_ARG: m < 1, a null
+ * pointer, an entry that is not finite, an unknown fn, a bad param, an eigenvalue outside the function's domain (theta < 0 for
+ * CGX_FN_SQRT; theta <= 0 for CGX_FN_INVSQRT, CGX_FN_INV, CGX_FN_LOG).  CGX_ERR_UNSUPPORTED: no convergence within 60 sweeps. */
+enum { CGX_FN_SQRT = 0, CGX_FN_INVSQRT = 1, CGX_FN_INV = 2, CGX_FN_LOG = 3, CGX_FN_EXP = 4 };
+cgx_status  cgx_tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef,
+                                 double *theta_minmax);
+/* X_j ~ f(A) B_j for nvec <= CGX_MAX_RHS vectors, one per ROW (B[j*ldb + i], X[j*ldx + i]), by `steps` steps of Lanczos: with V_m
+ * the Lanczos vectors of B_j and T_m their Jacobi matrix, x = ||b|| V_m f(T_m) e_1.  The recurrence is cgx_lanczos's, bit for bit
+ * (the same kernels, kernel width and freezing rule, m_j = the steps column j made), with the normalised v_t of every step kept on
+ * the device: 8 steps nvec lda bytes (4.3 GB at n = 32768, 16 vectors, 1024 steps), a block of its own that is made on first use,
+ * made again when a call needs more and freed with the problem; a failed allocation is CGX_ERR_OOM with the size in
+ * cgx_last_error and leaves the context usable.  No reorthogonalisation.  c_j = sqrt(z2_j) cgx_tridiag_function(m_j, alpha_j,
+ * beta_j, fn, param), one multiplication per entry, z2_j = ||B_j||^2 as the device summed it; X_j[i] = sum over t < m_j of
+ * c_j[t] v_(j,t)[i], ONE fma chain per element in ascending t from +0.0 (csrc/cgx_funm.hip).  From 64 steps on the columns'
+ * coefficients are made on one host thread per column (up to nvec x 30 MB of transient host memory at 1024 steps).  Column j's
+ * result depends on (A, B_j, fn, param, steps, the kernel width of nvec: 1, 2, 4, 8 or 16) only: permuting the columns permutes
+ * X bit for bit.
+ * steps_done (nvec ints: m_j), change (nvec doubles) and coef (nvec rows of `steps` doubles: c_j, zero at t >= m_j) may each be
+ * NULL; X is written only when the call succeeds.  change[j] is a convergence INDICATOR, not a bound: with m = m_j and lag = m -
+ * max(1, m / 8) (integer division), || c(m) - pad(c(lag)) || / || c(m) || with c(lag) made from the leading lag x lag block of T, sums
+ * in ascending t; 1 when lag = 0, 0 when || c(m) || = 0.  In exact arithmetic it is || x_m - x_lag || / || x_m ||.
+ * One GPU (CGX_COMM_SELF) and dense storage only, else CGX_ERR_UNSUPPORTED; a preconditioner that is set is CGX_ERR_UNSUPPORTED too
+ * (f(M^-1/2 A M^-1/2) is another quantity).  CGX_ERR_BAD_ARG: no matrix, steps < 1, steps > n or steps > CGX_MAX_LANCZOS_STEPS,
+ * nvec outside 1 .. CGX_MAX_RHS, a null B or X, ldb < n or ldx < n, an unknown fn or a bad param (all before any GPU work), a start
+ * vector of norm 0 or not finite (its column in cgx_last_error), a Ritz value outside the function's domain: "matrix is not
+ * positive definite", the value and the column in cgx_last_error.  A failed call leaves the context usable; the single path's
+ * plan and state are left as they were. */
+cgx_status  cgx_apply_function(cgx_ctx *ctx, int fn, double param, int nvec, int steps, const double *B, long ldb, double *X, long ldx,
+                               int *steps_done, double *change, double *coef);
+/* TEST PROBE: the combine kernel of cgx_apply_function by itself.  Q[((size_t)t*nvec + j)*ldq + i] is the caller's basis (steps
+ * slots of nvec vectors), C nvec rows of `steps` coefficients, m nvec step counts in 0 .. steps: X_j[i] = sum over t < m[j] of
+ * C[j*steps + t] Q[..], as above; slots at t >= m[j] are not read.  Same scope as cgx_apply_function (a problem must be set: it
+ * gives n and the row pitch). */
+cgx_status  cgx_probe_funm_combine(cgx_ctx *ctx, int nvec, int steps, const int *m, const double *Q, long ldq, const double *C,
+                                   double *X, long ldx);
+
 /* ---- kernel probes (parity tests of the individual hot ops through the C ABI) ------------- */
 /* Ap = A_shard * p  (K1; cblas_dgemv at cg.cc:101-102) for every local shard; y receives the n
  * results in global row order (LOOPBACK/SELF) or this rank's rows at their global offset (RCCL);
