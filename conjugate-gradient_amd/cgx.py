@@ -43,12 +43,17 @@ EXPORTS = [
     "cgx_lanczos", "cgx_trace_slq", "cgx_tridiag_quadrature",
     "cgx_lanczos_pc", "cgx_precond_logdet", "cgx_slq_probes", "cgx_trace_slq_pc",
     "cgx_tridiag_function", "cgx_apply_function", "cgx_probe_funm_combine",
+    "cgx_tridiag_eigenvectors", "cgx_eigenpairs", "cgx_probe_eigs_basis", "cgx_probe_eigs_orthogonalise",
 ]
 MAX_RHS = 16   # CGX_MAX_RHS: right-hand sides of one cgx_solve_multi call
 MAX_LANCZOS_STEPS = 1024   # CGX_MAX_LANCZOS_STEPS
 MAX_PROBES = 256           # CGX_MAX_PROBES
 SLQ_LOG, SLQ_INV = 0, 1    # cgx_trace_slq's fn
 FN_SQRT, FN_INVSQRT, FN_INV, FN_LOG, FN_EXP = 0, 1, 2, 3, 4   # CGX_FN_*: cgx_apply_function's and cgx_tridiag_function's fn
+EIG_LARGEST, EIG_SMALLEST = 0, 1   # CGX_EIG_*: cgx_eigenpairs's which
+MAX_EIGENPAIRS = 16                # CGX_MAX_EIGENPAIRS
+EIGS_SLOT_CHUNK = 32               # kEigsChunk (csrc/cgx_kernels.h): basis slots per workgroup of the projection kernel
+_EIG_NAMES = {"largest": EIG_LARGEST, "smallest": EIG_SMALLEST}
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 PRECOND_PIVCHOL = 2                   # the pivoted-Cholesky low-rank factor: one GPU, dense storage
@@ -178,6 +183,10 @@ def lib():
         L.cgx_tridiag_function.argtypes = [C.c_int, dp, dp, C.c_int, C.c_double, dp, dp]
         L.cgx_apply_function.argtypes = [vp, C.c_int, C.c_double, C.c_int, C.c_int, dp, C.c_long, dp, C.c_long, ip, dp, dp]
         L.cgx_probe_funm_combine.argtypes = [vp, C.c_int, C.c_int, ip, dp, C.c_long, dp, dp, C.c_long]
+        L.cgx_tridiag_eigenvectors.argtypes = [C.c_int, dp, dp, C.c_int, ip, dp, dp]
+        L.cgx_eigenpairs.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_double, dp, C.c_ulonglong, dp, dp, C.c_long, dp, dp, ip, ip]
+        L.cgx_probe_eigs_basis.argtypes = [vp, C.c_int, dp, dp, C.c_long, dp, dp, ip]
+        L.cgx_probe_eigs_orthogonalise.argtypes = [vp, C.c_int, dp, C.c_long, dp, dp, dp]
         L.cgx_set_preconditioner.argtypes = [vp, C.c_int]
         L.cgx_get_preconditioner.argtypes = [vp, ip]
         L.cgx_set_preconditioner_block.argtypes = [vp, C.c_int]
@@ -237,6 +246,25 @@ def tridiag_function(alpha, beta, fn, param=0.0):
         raise CgxError(st, "cgx_tridiag_function: %s (eigenvalues of T in [%r, %r])"
                        % (lib().cgx_status_string(st).decode(errors="replace"), mm[0], mm[1]))
     return coef[:m], mm[0], mm[1]
+
+
+def tridiag_eigenvectors(alpha, beta, index):
+    """Host only: (theta, S) for the Jacobi matrix with diagonal alpha (m entries) and off-diagonal beta (at least m - 1 entries, the
+    rest is not read): theta all m eigenvalues ascending, S[c] the unit eigenvector of the index[c]-th of them, its first component
+    >= 0 (include/cgx.h cgx_tridiag_eigenvectors)."""
+    alpha = np.ascontiguousarray(alpha, dtype=np.float64).reshape(-1)
+    beta = np.ascontiguousarray(beta, dtype=np.float64).reshape(-1)
+    index = np.ascontiguousarray(index, dtype=np.int32).reshape(-1)
+    m = alpha.size
+    if beta.size < m - 1:
+        raise ValueError("beta must have at least m - 1 entries")
+    theta = np.zeros(max(m, 1), dtype=np.float64)
+    S = np.zeros((max(index.size, 1), max(m, 1)), dtype=np.float64)
+    st = lib().cgx_tridiag_eigenvectors(int(m), _dp(alpha), _dp(beta) if beta.size else None, int(index.size),
+                                        index.ctypes.data_as(C.POINTER(C.c_int)), _dp(theta), _dp(S))
+    if st:
+        raise CgxError(st, "cgx_tridiag_eigenvectors: %s" % lib().cgx_status_string(st).decode(errors="replace"))
+    return theta[:m], S[:index.size, :m]
 
 
 def parse_matrix_market(path, threads=0):
@@ -618,6 +646,54 @@ class CGSolver:
         self._check(lib().cgx_probe_funm_combine(self._h, int(Q.shape[1]), int(Q.shape[0]), m.ctypes.data_as(C.POINTER(C.c_int)), _dp(Q),
                                                  int(Q.shape[2]), _dp(Cf), _dp(X), int(X.shape[1])))
         return X
+
+    def eigenpairs(self, k, which="largest", steps=None, tol=0.0, v0=None, seed=1):
+        """The k largest (which = "largest", descending) or smallest ("smallest", ascending) eigenvalues of the current symmetric,
+        dense matrix and their eigenvectors by Lanczos with full reorthogonalisation (include/cgx.h cgx_eigenpairs): at most `steps`
+        steps (default min(n, MAX_LANCZOS_STEPS, max(2 k + 20, 100))) from v0 (n doubles) or, with v0 = None, from the library's
+        Rademacher vector of `seed`; tol = 0 runs all steps, tol > 0 stops once the Ritz estimates are below tol max |theta|.
+        Returns (values, vectors, info): values (k,), vectors (k, n) one per row, info = dict(residual, estimate, steps_done,
+        nfound); entries at j >= nfound are 0."""
+        n, k = self.n(), int(k)
+        if steps is None:
+            steps = min(n, MAX_LANCZOS_STEPS, max(2 * k + 20, 100))
+        steps = int(steps)
+        if v0 is not None:
+            v0 = np.ascontiguousarray(v0, dtype=np.float64).reshape(-1)
+            assert v0.size == n, v0.shape
+        kk = max(k, 1)
+        values, residual, estimate = np.zeros(kk), np.zeros(kk), np.zeros(kk)
+        vectors = np.zeros((kk, n), dtype=np.float64)
+        done, found = C.c_int(), C.c_int()
+        self._check(lib().cgx_eigenpairs(self._h, _EIG_NAMES.get(which, which), k, steps, float(tol), None if v0 is None else _dp(v0),
+                                         int(seed), _dp(values), _dp(vectors), int(n), _dp(residual), _dp(estimate), C.byref(done),
+                                         C.byref(found)))
+        return values[:k], vectors[:k], {"residual": residual[:k], "estimate": estimate[:k], "steps_done": done.value,
+                                         "nfound": found.value}
+
+    def _probe_eigs_basis(self, v0, steps):
+        """Test hook: the recurrence of eigenpairs alone.  Returns (Q, alpha, beta, steps_done): Q has steps + 1 rows, slots 0 ..
+        m - 1 and, when the run was not frozen, the next vector q_m; the rows behind them are zero."""
+        v0 = np.ascontiguousarray(v0, dtype=np.float64).reshape(-1)
+        n, steps = self.n(), int(steps)
+        assert v0.size == n, v0.shape
+        Q = np.zeros((max(steps, 0) + 1, n), dtype=np.float64)
+        alpha, beta = np.zeros(max(steps, 1)), np.zeros(max(steps, 1))
+        done = C.c_int()
+        self._check(lib().cgx_probe_eigs_basis(self._h, steps, _dp(v0), _dp(Q), int(n), _dp(alpha), _dp(beta), C.byref(done)))
+        return Q, alpha[:steps], beta[:steps], done.value
+
+    def _probe_eigs_orthogonalise(self, Q, w, nslots=None):
+        """Test hook: one projection + subtraction pass of eigenpairs.  Q float64 (rows >= nslots, ldq >= n), w (>= n,): returns
+        (h, w_new) with h[s] = Q[s, :n] . w[:n] for s < nslots and w_new = w[:n] - h @ Q[:nslots, :n]."""
+        Q = np.ascontiguousarray(Q, dtype=np.float64)
+        w = np.ascontiguousarray(w, dtype=np.float64).reshape(-1)
+        n = self.n()
+        nslots = Q.shape[0] if nslots is None else int(nslots)
+        assert Q.ndim == 2 and Q.shape[1] >= n and Q.shape[0] >= nslots and w.size >= n
+        h, out = np.zeros(max(nslots, 1)), np.zeros(n)
+        self._check(lib().cgx_probe_eigs_orthogonalise(self._h, nslots, _dp(Q), int(Q.shape[1]), _dp(w), _dp(out), _dp(h)))
+        return h[:nslots], out
 
     def precond_logdet(self):
         """log det M of the preconditioner that is set (0.0 with none); makes the preconditioner if no call has made it yet."""

@@ -125,6 +125,9 @@ void free_problem(cgx_ctx *ctx)
     (void)hipFree(ctx->funm);
     ctx->funm = nullptr;
     ctx->funm_bytes = 0;
+    (void)hipFree(ctx->eigs);
+    ctx->eigs = nullptr;
+    ctx->eigs_bytes = 0;
     if (ctx->h_stage) (void)hipHostFree(ctx->h_stage);
     ctx->h_stage = nullptr;
     ctx->d_gathered_ptrs = nullptr;

@@ -204,6 +204,11 @@ struct cgx_ctx {
     // the problem
     double *funm = nullptr;
     size_t funm_bytes = 0;
+    // extreme eigenpairs (cgx_eigenpairs, cgx_eigs_host.cpp): the work vectors, partials, histories, the Ritz-vector block and the
+    // reorthogonalised basis ((steps + 1) x lda doubles of the call); made on first use, made again when a call needs more, freed
+    // with the problem
+    double *eigs = nullptr;
+    size_t eigs_bytes = 0;
 
     int fault_after = -1;     // >= 0: HIP_TRY calls left until one is made to fail (cgx_probe_set_fault_after, error-path tests only)
 
@@ -358,6 +363,9 @@ cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, cons
 bool funm_args_ok(int fn, double param);   // a known CGX_FN_*, and for CGX_FN_EXP a finite param >= 0
 enum class TridiagFn { ok, no_convergence, domain };
 TridiagFn tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *minmax, double *bad);
+// ... and with cgx_eigenpairs (cgx_eigs_host.cpp): all eigenvalues ascending into theta (may be null) and the unit eigenvectors of
+// index[0 .. nsel) as rows of S (m doubles each, first component >= 0); false: no convergence
+bool tridiag_eigenvectors(int m, const double *alpha, const double *beta, int nsel, const int *index, double *theta, double *S);
 
 // Lays a side block out in 128-byte aligned pieces; base == nullptr only measures (bytes()).
 struct Carver {

@@ -676,4 +676,49 @@ struct FunmArgs {
 };
 hipError_t launch_funm_combine(const FunmArgs &a, hipStream_t s);
 
+// ---- extreme eigenpairs by Lanczos with full reorthogonalisation (cgx_eigenpairs; cgx_eigs.hip) ------------
+// One start vector; the basis keeps one vector per slot, element i of q_s at Q[s * lda + i], steps + 1 slots.  A step is the plain
+// K1m at width 1 on slot t, then project(first) / subtract / project / subtract(second) / normalise.
+constexpr int kMaxEigenpairs = 16;             // = CGX_MAX_EIGENPAIRS
+constexpr int kEigsLive = 0x7fffffff;          // EigsScalars::m of a run that is still going
+constexpr int kEigsTile = 256;                 // rows per workgroup of the step kernels, = rows per projection partial
+constexpr int kEigsChunk = 32;                 // slots per projection workgroup (4 waves x 8)
+constexpr int kEigsSlotPitch = 1040;           // doubles per tile in the projection partials: kMaxLanczosSteps slots, 128-B lines
+struct EigsScalars {
+    double amax[2];            // max |alpha_s| over s < t at [t & 1]: step t reads that slot and writes the other
+    double z2;                 // ||v0||^2
+    int    m;                  // steps made before the run was frozen (kEigsLive: running; -1: bad start vector).  A step number,
+                               // not a flag, as LanczosScalars::m
+    int    bad;                // the start vector has norm 0 or is not finite
+};
+struct EigsArgs {
+    int n;
+    long lda;
+    int t;                     // the step; project / subtract run on slots 0 .. t
+    double *Q;                 // the basis
+    const double *Y;           // K1m's A q_t
+    double *W;                 // lda: the vector under orthogonalisation
+    const double *k1p;         // K1m's q_t . A q_t partials
+    int g1;
+    double *hp;                // eigs_tiles(n) x kEigsSlotPitch: the projection partials, [tile][slot]
+    double *h;                 // kEigsSlotPitch: the folded h of the latest subtraction (the probe reads it)
+    double *wwp;               // eigs_tiles(n): the ||w||^2 partials of the second subtraction
+    double *alpha, *beta;      // the histories, kMaxLanczosSteps each
+    EigsScalars *sc;
+};
+int eigs_tiles(int n);
+// q_0 = v0 / ||v0|| in place (n doubles at q0), the scalars reset; a zero or non-finite v0 is marked bad and no step runs.
+hipError_t launch_eigs_init(int n, double *q0, EigsScalars *sc, hipStream_t s);
+// first: alpha_t, w = y - alpha_t q_t - beta_(t-1) q_(t-1) into W, and the partials of Q_t^T w; else the partials from W as it is.
+hipError_t launch_eigs_project(const EigsArgs &a, bool first, hipStream_t s);
+// h folded in ascending tile order, W -= Q_t h; second: also the ||w||^2 partials.
+hipError_t launch_eigs_subtract(const EigsArgs &a, bool second, hipStream_t s);
+// beta_t, the breakdown test, q_(t+1) = W / beta_t into slot t + 1.
+hipError_t launch_eigs_normalise(const EigsArgs &a, hipStream_t s);
+// X_j[i] = sum over t < m of C[t * width + j] q_t[i], j < nev, width = multi_width(nev): the basis is read once for all vectors.
+hipError_t launch_eigs_combine(int n, long lda, int m, int nev, const double *Q, const double *C, double *X, long ldx, hipStream_t s);
+// out[j] = || Y_j - theta_j X_j ||^2, one workgroup per vector, fixed order.
+hipError_t launch_eigs_residual(int n, long lda, int nev, const double *Y, const double *X, const double *theta, double *out,
+                                hipStream_t s);
+
 }  // namespace cgx

@@ -277,7 +277,54 @@ cgxi::TridiagFn cgxi::tridiag_function(int m, const double *alpha, const double 
     return TridiagFn::ok;
 }
 
+// Selected unit eigenvectors of the m x m Jacobi matrix (alpha, beta), entries already checked: the same recorded sweep, T = S diag(d)
+// S^T, so the eigenvector of d_k is S e_k -- the recorded rotations applied to e_k from the last one back, O(m^2) each, nothing m x m
+// held.  theta (may be null): all eigenvalues ascending (ties by their place in d); index[c] counts in that order; row c of S (m
+// doubles) is signed so that its first component is >= 0.  false: no convergence.
+bool cgxi::tridiag_eigenvectors(int m, const double *alpha, const double *beta, int nsel, const int *index, double *theta, double *S)
+{
+    std::vector<double> work((size_t)3 * m, 0.0);
+    std::vector<Rotation> rot;
+    rot.reserve((size_t)m * m + (size_t)m * m / 4 + 64);
+    std::vector<int> idx((size_t)m);
+    double *d = work.data(), *e = d + m, *z = e + m;
+    for (int i = 0; i < m; ++i) {
+        d[i] = alpha[i];
+        if (i + 1 < m) e[i] = beta[i];
+        idx[i] = i;
+    }
+    z[0] = 1.0;
+    if (!ql_first_row(m, d, e, z, &rot)) return false;
+    std::sort(idx.begin(), idx.end(), [&](int a, int b) { return d[a] < d[b] || (d[a] == d[b] && a < b); });
+    if (theta)
+        for (int i = 0; i < m; ++i) theta[i] = d[idx[i]];
+    for (int c = 0; c < nsel; ++c) {
+        double *v = S + (size_t)c * m;
+        std::fill(v, v + m, 0.0);
+        v[idx[index[c]]] = 1.0;
+        for (size_t r = rot.size(); r-- > 0;) {
+            const Rotation &q = rot[r];
+            const double a = v[q.i], b = v[q.i + 1];
+            v[q.i] = q.c * a + q.s * b;
+            v[q.i + 1] = q.c * b - q.s * a;
+        }
+        if (v[0] < 0.0)
+            for (int i = 0; i < m; ++i) v[i] = -v[i];
+    }
+    return true;
+}
+
 extern "C" {
+
+cgx_status cgx_tridiag_eigenvectors(int m, const double *alpha, const double *beta, int nsel, const int *index, double *theta, double *S)
+{
+    if (m < 1 || !alpha || !S || (m > 1 && !beta) || nsel < 1 || !index) return CGX_ERR_BAD_ARG;
+    for (int i = 0; i < m; ++i)
+        if (!std::isfinite(alpha[i]) || (i + 1 < m && !std::isfinite(beta[i]))) return CGX_ERR_BAD_ARG;
+    for (int c = 0; c < nsel; ++c)
+        if (index[c] < 0 || index[c] >= m) return CGX_ERR_BAD_ARG;
+    return tridiag_eigenvectors(m, alpha, beta, nsel, index, theta, S) ? CGX_OK : CGX_ERR_UNSUPPORTED;   // (no convergence in 60 sweeps)
+}
 
 cgx_status cgx_tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *theta_minmax)
 {

@@ -32,6 +32,11 @@
 // cgx_apply_function): NAME = sqrt, invsqrt, inv, log or exp (exp(-T A)), M Lanczos steps (default 100, at most min(n, 1024)).  The
 // result goes where the solution goes; the timing line in OUTFILE is written as ever and one line with the steps made, the convergence
 // indicator and ||x|| follows on stdout.  One GPU, dense storage, no preconditioner, not with --shifts or --logdet.
+// `--eigs K[,M[,largest|smallest]]` (NOT a reference mode) computes the K largest (default) or smallest eigenvalues of the matrix instead
+// of solving (include/cgx.h cgx_eigenpairs): at most M steps (default 100, at most min(n, 1024)) of Lanczos with full
+// reorthogonalisation from the library's start vector (seed 1), tol = 0.  The timing line in OUTFILE is written as ever; one line
+// with the steps follows on stdout, then one per eigenvalue with its residual.  One GPU, dense storage, no preconditioner, not
+// with --shifts, --logdet or --apply; the matrix must be symmetric.
 #include <signal.h>
 #include <sys/wait.h>
 #include <unistd.h>
@@ -177,6 +182,10 @@ int usage(const char *prog)
               << "                                  M Lanczos steps (default 100); NAME = sqrt, invsqrt, inv, log or exp (exp(-T A),\n"
               << "                                  T >= 0, default 1); one GPU, dense storage, no preconditioner, not with --shifts\n"
               << "                                  or --logdet; prints one line\n"
+              << "         --eigs K[,M[,largest|smallest]]  opt-in, not in the reference: the K (1 ... 16) largest (default) or smallest\n"
+              << "                                  eigenvalues of the matrix instead of solving, by at most M steps (default 100) of\n"
+              << "                                  Lanczos with full reorthogonalisation; one GPU, dense storage, no preconditioner,\n"
+              << "                                  not with --shifts, --logdet or --apply; prints one line per eigenvalue\n"
               << "         --stats                  also print iterations/s and K1 GB/s on stderr (event-times every K1:\n"
               << "                                  the seconds in OUTFILE are then a few % higher)" << std::endl;
     return 1;
@@ -206,6 +215,7 @@ int main(int argc, char **argv)
     int apply_fn = -1, apply_steps = 100;        // --apply NAME[,M[,T]] (-1: off)
     double apply_param = 1.0;
     std::string apply_name;
+    int eigs_nev = 0, eigs_steps = 100, eigs_which = CGX_EIG_LARGEST;   // --eigs K[,M[,largest|smallest]] (0: off)
     double wireup_timeout = 120.0;
     if (const char *e = getenv("CG_WIREUP_TIMEOUT")) wireup_timeout = atof(e);
     if (const char *e = getenv("CG_NGPU")) ngpu = atoi(e);
@@ -300,6 +310,25 @@ int main(int argc, char **argv)
                 return usage(argv[0]);
             }
         }
+        else if (a == "--eigs" && i + 1 < argc) {
+            const std::string arg(argv[++i]);
+            std::vector<std::string> part;
+            std::stringstream list(arg);
+            std::string item;
+            while (std::getline(list, item, ',')) part.push_back(item);
+            bool ok = !part.empty() && part.size() <= 3 && arg.back() != ',' && parse_int(part[0], &eigs_nev);
+            if (ok && part.size() >= 2) ok = parse_int(part[1], &eigs_steps);
+            if (ok && part.size() == 3) {
+                ok = part[2] == "largest" || part[2] == "smallest";
+                eigs_which = part[2] == "smallest" ? CGX_EIG_SMALLEST : CGX_EIG_LARGEST;
+            }
+            if (!ok || eigs_nev < 1 || eigs_nev > CGX_MAX_EIGENPAIRS || eigs_steps < eigs_nev || eigs_steps > CGX_MAX_LANCZOS_STEPS) {
+                std::cerr << argv[0] << ": --eigs takes K[,M[,largest|smallest]] with 1 <= K <= " << CGX_MAX_EIGENPAIRS << " eigenvalues and K <= M <= "
+                          << CGX_MAX_LANCZOS_STEPS << " steps, not '" << arg << "'\n";
+                eigs_nev = 0;
+                return usage(argv[0]);
+            }
+        }
         else if (a == "--transport" && i + 1 < argc) transport = argv[++i];
         else if (a == "--wireup-timeout" && i + 1 < argc) wireup_timeout = atof(argv[++i]);
         else if (a == "--same-device") same_device = true;   // rehearsal: every rank on device 0 (p2p only)
@@ -340,6 +369,10 @@ int main(int argc, char **argv)
     }
     if (apply_fn >= 0 && (shifted || jacobi || pivchol || logdet_probes || logdet_pc_probes)) {
         std::cerr << argv[0] << ": --apply runs without a preconditioner and not together with --shifts or --logdet\n";
+        return usage(argv[0]);
+    }
+    if (eigs_nev && (shifted || jacobi || pivchol || logdet_probes || logdet_pc_probes || apply_fn >= 0)) {
+        std::cerr << argv[0] << ": --eigs runs without a preconditioner and not together with --shifts, --logdet or --apply\n";
         return usage(argv[0]);
     }
     if (ngpu < 1) ngpu = 1;
@@ -573,6 +606,8 @@ int main(int argc, char **argv)
         double slq_pc = 0;                                   // --logdet-pc: log det of the preconditioner
         int apply_done = 0;                                  // --apply: the steps made and the convergence indicator
         double apply_change = 0;
+        double eig_val[CGX_MAX_EIGENPAIRS] = {0}, eig_res[CGX_MAX_EIGENPAIRS] = {0}, eig_est[CGX_MAX_EIGENPAIRS] = {0};   // --eigs
+        int eig_done = 0, eig_found = 0;
         if (logdet_probes) {
             if (cgx_trace_slq(solver.context(), CGX_SLQ_LOG, logdet_probes, logdet_steps, 1ull, nullptr, 0, &slq[0], &slq[1], nullptr,
                               &slq[2]) != CGX_OK)
@@ -589,6 +624,11 @@ int main(int argc, char **argv)
                 cgx_apply_function(solver.context(), apply_fn, apply_param, 1, apply_steps, b.data(), n, x_d.data(), n, &apply_done, &apply_change,
                                    nullptr) != CGX_OK)
                 throw std::runtime_error(std::string("--apply: ") + cgx_last_error(solver.context()));
+        }
+        else if (eigs_nev) {
+            if (cgx_eigenpairs(solver.context(), eigs_which, eigs_nev, eigs_steps, 0.0, nullptr, 1ull, eig_val, nullptr, 0, eig_res, eig_est,
+                               &eig_done, &eig_found) != CGX_OK)
+                throw std::runtime_error(std::string("--eigs: ") + cgx_last_error(solver.context()));
         }
         else if (shifted) solver.solve_shifted(shifts, x_shifted);
         else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
@@ -618,6 +658,13 @@ int main(int argc, char **argv)
                 std::cout << "\t[APPLY] fn = " << apply_name << ", steps = " << apply_steps << ", steps_done = " << apply_done
                           << ", change = " << std::setprecision(12) << apply_change << ", ||x|| = " << std::sqrt(xx) << std::setprecision(6)
                           << std::endl;
+            }
+            if (eigs_nev) {
+                std::cout << "\t[EIGS] which = " << (eigs_which == CGX_EIG_SMALLEST ? "smallest" : "largest") << ", nev = " << eigs_nev
+                          << ", steps = " << eigs_steps << ", steps_done = " << eig_done << ", nfound = " << eig_found << std::endl;
+                for (int j = 0; j < eig_found; ++j)
+                    std::cout << "\t[EIG " << j << "] value = " << std::setprecision(17) << eig_val[j] << ", residual = " << std::setprecision(12)
+                              << eig_res[j] << ", estimate = " << eig_est[j] << std::setprecision(6) << std::endl;
             }
             if (shifted) {
                 const std::vector<cgx_result> &sr = solver.shift_results();

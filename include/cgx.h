@@ -505,6 +505,61 @@ cgx_status  cgx_apply_function(cgx_ctx *ctx, int fn, double param, int nvec, int
 cgx_status  cgx_probe_funm_combine(cgx_ctx *ctx, int nvec, int steps, const int *m, const double *Q, long ldq, const double *C,
                                    double *X, long ldx);
 
+/* ---- extreme eigenpairs: Lanczos with full reorthogonalisation ---- */
+enum { CGX_EIG_LARGEST = 0, CGX_EIG_SMALLEST = 1 };
+#define CGX_MAX_EIGENPAIRS 16
+/* HOST ONLY, no context: eigenvalues and selected eigenvectors of the Jacobi matrix T of cgx_tridiag_quadrature's arguments (beta may
+ * be NULL for m = 1).  theta (m doubles, may be NULL) receives all eigenvalues in ascending order; index[c], c < nsel, is in 0 .. m-1
+ * and counts in that order (repeats are allowed); row c of S (nsel rows of m doubles) is the unit eigenvector of index[c], signed so
+ * that its first component is >= 0.  The recorded QL sweep of cgx_tridiag_function: eigenvector k is the recorded rotations applied
+ * in reverse to e_k, O(m^2) per vector, nothing m x m is held, no LAPACK.  CGX_ERR_BAD_ARG: m < 1, a null alpha, S or index, a null
+ * beta with m > 1, an entry that is not finite, nsel < 1, an index out of range.  CGX_ERR_UNSUPPORTED: no convergence within 60
+ * sweeps. */
+cgx_status  cgx_tridiag_eigenvectors(int m, const double *alpha, const double *beta, int nsel, const int *index,
+                                    double *theta, double *S);
+/* The nev largest (CGX_EIG_LARGEST) or smallest (CGX_EIG_SMALLEST) eigenvalues of the current matrix and their eigenvectors, from at
+ * most `steps` steps of Lanczos on ONE start vector with the basis kept orthogonal (csrc/cgx_eigs.hip).  A is taken as symmetric
+ * (not checked) and need not be positive definite.  v0: n doubles, or NULL for probe 0 of cgx_trace_slq's Rademacher hash of `seed`
+ * (seed is not read otherwise).  With q_0 = v0 / ||v0||, step t:
+ *   y = A q_t (cgx_solve_multi's plain K1 at width 1), alpha_t = q_t . y from its partials in a fixed order;
+ *   w = y - alpha_t q_t - beta_(t-1) q_(t-1);  twice: h = Q_t^T w over slots 0 .. t, w = w - Q_t h (classical Gram-Schmidt, twice:
+ *   per slot the partials of 256-row tiles added in ascending tile order, per element one fma chain over the slots in ascending
+ *   order from +0.0);  beta_t = ||w||;  beta_t <= 2^-36 max_(s<=t) |alpha_s|: the space is invariant, the run is frozen with m = t + 1
+ *   (decided on the device: the launches behind it exit at once); else q_(t+1) = w / beta_t.
+ * T_m has alpha as first computed and beta behind the reorthogonalisation.  tol = 0: all `steps` steps run.  tol > 0: behind every
+ * step with (t + 1) mod 16 = 0, and behind the last one, the host reads alpha and beta, forms the wanted Ritz pairs of T and
+ * estimate_j = beta_t |s_(t,j)| (s_j: the unit eigenvector of T, its last component) and stops once every wanted estimate is <=
+ * tol max |theta| over all Ritz values of T.
+ * values[j], j < nev: descending for CGX_EIG_LARGEST, ascending for CGX_EIG_SMALLEST.  vectors[j*ldv + i] = sum over t < m of
+ * s_j[t] q_t[i], one fma chain per element in ascending t from +0.0, the sign that of s_j[0] >= 0; the basis is read once for all
+ * nev vectors.  residual[j] = ||A x_j - theta_j x_j|| from one more plain K1 on the nev vectors: a true residual, the basis is not
+ * used for it.  estimate[j] as above.  *steps_done = m; *nfound = min(nev, m), and entries at j >= nfound are 0.  vectors, residual,
+ * estimate, steps_done and nfound may each be NULL; outputs are written only when the call succeeds.  The result depends on (A, v0
+ * or seed, which, nev, steps, tol) only, and a run of more steps has the shorter run's alpha_t, beta_t and q_t as a bitwise prefix.
+ * With an exactly multiple eigenvalue a single start vector finds ONE vector of its eigenspace (the Krylov space holds no more):
+ * the value comes back once, and the next entry is the next distinct eigenvalue.  No restarts: the basis takes 8 (steps + 1) lda
+ * bytes on the device in a block of its own, made on first use, made again when a call needs more, freed with the problem; a
+ * failed allocation is CGX_ERR_OOM with the size in cgx_last_error.
+ * Scope, checks and their order are cgx_lanczos's: one GPU (CGX_COMM_SELF), dense storage and no preconditioner set, else
+ * CGX_ERR_UNSUPPORTED; steps in 1 .. min(n, CGX_MAX_LANCZOS_STEPS), else CGX_ERR_BAD_ARG.  Then CGX_ERR_BAD_ARG before any GPU work:
+ * an unknown `which`, nev outside 1 .. CGX_MAX_EIGENPAIRS or > steps, tol negative or not finite, a null values, ldv < n with vectors
+ * given; and from the device a start vector of norm 0 or not finite.  A failed call leaves the context usable; the single path's
+ * plan and state and the blocks of the other entry points are left as they were. */
+cgx_status  cgx_eigenpairs(cgx_ctx *ctx, int which, int nev, int steps, double tol, const double *v0,
+                          unsigned long long seed, double *values, double *vectors, long ldv,
+                          double *residual, double *estimate, int *steps_done, int *nfound);
+/* TEST PROBE: the recurrence of cgx_eigenpairs alone (tol = 0) from v0 (not NULL).  alpha, beta: `steps` doubles, zero at t >=
+ * *steps_done = m.  Q[t*ldq + i] receives slots 0 .. m-1 and, when no step froze the run (then m = steps), also slot m, the next
+ * vector: Q must hold steps + 1 rows; rows that are not written keep what they held.  Scope and refusals as cgx_eigenpairs. */
+cgx_status  cgx_probe_eigs_basis(cgx_ctx *ctx, int steps, const double *v0, double *Q, long ldq,
+                                double *alpha, double *beta, int *steps_done);
+/* TEST PROBE: ONE projection + subtraction pass of cgx_eigenpairs on the caller's slots Q[s*ldq + i], s < nslots <=
+ * CGX_MAX_LANCZOS_STEPS, and w_in (n doubles): h_out[s] = q_s . w_in, w_out = w_in - sum_s h_out[s] q_s, in the kernels' orders.  On
+ * the device the slots, the slot behind them and the vector are filled with NaN over their whole row pitch before the upload.  A
+ * problem must be set (it gives n and the row pitch); one GPU and dense storage. */
+cgx_status  cgx_probe_eigs_orthogonalise(cgx_ctx *ctx, int nslots, const double *Q, long ldq,
+                                        const double *w_in, double *w_out, double *h_out);
+
 /* ---- kernel probes (parity tests of the individual hot ops through the C ABI) ------------- */
 /* Ap = A_shard * p  (K1; cblas_dgemv at cg.cc:101-102) for every local shard; y receives the n
  * results in global row order (LOOPBACK/SELF) or this rank's rows at their global offset (RCCL);
