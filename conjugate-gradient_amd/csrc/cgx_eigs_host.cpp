@@ -4,7 +4,7 @@
 // One GPU, dense storage, no preconditioner, one start vector.  A step is six launches -- the plain multi-vector K1 of cgx_multi.hip
 // at width 1 as it is, then the five kernels of cgx_eigs.hip -- and with tol = 0 nothing is polled: the steps are queued behind each
 // other and one synchronisation ends them.  With tol > 0 the host reads alpha and beta behind every 16th step, forms the wanted Ritz
-// pairs of T (tridiag_eigenvectors, cgx_lanczos_host.cpp) and stops once their estimates are small.  The Ritz vectors are one launch
+// pairs of T (tridiag_eigenvectors, cgx_tridiag.cpp) and stops once their estimates are small.  The Ritz vectors are one launch
 // of k_eigs_combine over the basis, their residuals one more plain K1m on them and k_eigs_residual.  Everything lives in ONE device
 // allocation of the context (cgx_ctx::eigs), apart from every other path's buffers.
 #include "cgx_internal.h"
@@ -58,18 +58,9 @@ size_t eigs_layout(const cgx_ctx *ctx, double *base, int steps, EigsView *v)
 // The block for a call of `steps`: made on first use, made again when this call needs more than it holds.
 cgx_status ensure_eigs(cgx_ctx *ctx, const std::string &fn, int steps, EigsView *v)
 {
-    const size_t bytes = eigs_layout(ctx, nullptr, steps, v);
-    if (ctx->eigs && ctx->eigs_bytes < bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->eigs);
-        ctx->eigs = nullptr;
-        ctx->eigs_bytes = 0;
-    }
-    const cgx_status st = ensure_side_block(ctx, &ctx->eigs, &ctx->eigs_bytes, bytes);
-    if (st == CGX_ERR_OOM)
-        return fail(ctx, CGX_ERR_OOM, fn + ": no device memory for the Lanczos basis: " + std::to_string(bytes) + " bytes (8 (steps + 1) lda = " +
-                                          std::to_string(steps + 1) + " x " + std::to_string(ctx->lda) + " doubles, and the work vectors)");
-    CGX_TRY(st);
+    CGX_TRY(ensure_growing_block(ctx, &ctx->eigs, &ctx->eigs_bytes, eigs_layout(ctx, nullptr, steps, v), fn,
+                                 "8 (steps + 1) lda = " + std::to_string(steps + 1) + " x " + std::to_string(ctx->lda) +
+                                     " doubles, and the work vectors"));
     eigs_layout(ctx, ctx->eigs, steps, v);
     return CGX_OK;
 }
@@ -107,15 +98,7 @@ cgx_status eigs_steps(cgx_ctx *ctx, const EigsView &v, int t0, int t1)
 {
     hipStream_t st = ctx->stream;
     for (int t = t0; t < t1; ++t) {
-        cgx::MultiArgs g{};
-        g.A = ctx->shards[0].A;
-        g.lda = ctx->lda;
-        g.n = ctx->n;
-        g.nrhs = 1;
-        g.v = v.Q + (size_t)t * ctx->lda;
-        g.Y = v.Y;
-        g.partials = v.k1p;
-        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
+        HIP_TRY(ctx, cgx::launch_multi_gemv(plain_k1m_args(ctx, 1, v.Q + (size_t)t * ctx->lda, v.Y, v.k1p), false, st));
         const cgx::EigsArgs a = step_args(ctx, v, t);
         HIP_TRY(ctx, cgx::launch_eigs_project(a, true, st));
         HIP_TRY(ctx, cgx::launch_eigs_subtract(a, false, st));
@@ -170,11 +153,6 @@ bool ritz_pairs(int m, const double *alpha, const double *beta, int which, int n
     return true;
 }
 
-double rademacher0(unsigned long long seed_mixed, unsigned long long i)   // probe 0 of cgx_trace_slq's hash (include/cgx.h)
-{
-    return (cgx::hash_mix64(seed_mixed ^ i) >> 63) ? -1.0 : 1.0;
-}
-
 }  // namespace
 
 extern "C" {
@@ -183,7 +161,7 @@ cgx_status cgx_eigenpairs(cgx_ctx *ctx, int which, int nev, int steps, double to
                           double *vectors, long ldv, double *residual, double *estimate, int *steps_done, int *nfound)
 {
     const std::string name("cgx_eigenpairs");
-    CGX_TRY(check_lanczos(ctx, "cgx_eigenpairs", steps));
+    CGX_TRY(check_lanczos(ctx, name, steps));
     if (which != CGX_EIG_LARGEST && which != CGX_EIG_SMALLEST)
         return fail(ctx, CGX_ERR_BAD_ARG, name + ": which must be CGX_EIG_LARGEST or CGX_EIG_SMALLEST");
     if (nev < 1 || nev > CGX_MAX_EIGENPAIRS || nev > steps) return fail(ctx, CGX_ERR_BAD_ARG, name + ": nev must be 1 .. min(steps, CGX_MAX_EIGENPAIRS)");
@@ -200,7 +178,7 @@ cgx_status cgx_eigenpairs(cgx_ctx *ctx, int which, int nev, int steps, double to
     if (!v0) {
         const unsigned long long sm = cgx::hash_mix64(seed);
         start.resize((size_t)n);
-        for (int i = 0; i < n; ++i) start[(size_t)i] = rademacher0(sm, (unsigned long long)i);
+        for (int i = 0; i < n; ++i) start[(size_t)i] = cgx::rademacher_sign(sm, 0, (unsigned long long)i);   // probe 0 of cgx_trace_slq
     }
     std::vector<double> alpha((size_t)steps), beta((size_t)steps);
     CGX_TRY(eigs_begin(ctx, v, v0 ? v0 : start.data()));
@@ -231,20 +209,10 @@ cgx_status cgx_eigenpairs(cgx_ctx *ctx, int which, int nev, int steps, double to
     HIP_TRY(ctx, hipMemcpyAsync(v.C, coef.data(), coef.size() * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(v.theta, rz.value, (size_t)nf * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, cgx::launch_eigs_combine(n, ctx->lda, m, nf, v.Q, v.C, v.X, ctx->lda, st));
-    cgx::MultiArgs g{};
-    g.A = ctx->shards[0].A;
-    g.lda = ctx->lda;
-    g.n = n;
-    g.nrhs = nf;
-    g.v = v.X;
-    g.Y = v.YX;
-    g.partials = v.k1p;
-    HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
+    HIP_TRY(ctx, cgx::launch_multi_gemv(plain_k1m_args(ctx, nf, v.X, v.YX, v.k1p), false, st));
     HIP_TRY(ctx, cgx::launch_eigs_residual(n, ctx->lda, nf, v.YX, v.X, v.theta, v.rn, st));
     HIP_TRY(ctx, hipMemcpyAsync(rn, v.rn, (size_t)nf * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (vectors)
-        HIP_TRY(ctx, hipMemcpy2DAsync(vectors, (size_t)ldv * sizeof(double), v.X, (size_t)ctx->lda * sizeof(double), (size_t)n * sizeof(double), nf,
-                                      hipMemcpyDeviceToHost, st));
+    if (vectors) CGX_TRY(download_columns(ctx, vectors, ldv, v.X, nf));
     HIP_TRY(ctx, hipStreamSynchronize(st));
 
     for (int j = 0; j < nev; ++j) {
@@ -263,7 +231,7 @@ cgx_status cgx_eigenpairs(cgx_ctx *ctx, int which, int nev, int steps, double to
 cgx_status cgx_probe_eigs_basis(cgx_ctx *ctx, int steps, const double *v0, double *Q, long ldq, double *alpha, double *beta, int *steps_done)
 {
     const std::string name("cgx_probe_eigs_basis");
-    CGX_TRY(check_lanczos(ctx, "cgx_probe_eigs_basis", steps));
+    CGX_TRY(check_lanczos(ctx, name, steps));
     if (!v0 || !Q || !alpha || !beta || !steps_done) return fail(ctx, CGX_ERR_BAD_ARG, name + ": null pointer");
     if (ldq < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, name + ": leading dimension smaller than n");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -276,8 +244,7 @@ cgx_status cgx_probe_eigs_basis(cgx_ctx *ctx, int steps, const double *v0, doubl
     CGX_TRY(eigs_steps(ctx, v, 0, steps));
     CGX_TRY(eigs_read(ctx, name, v, steps, a.data(), b.data(), &m, &live));
     const int rows = live ? steps + 1 : m;
-    HIP_TRY(ctx, hipMemcpy2DAsync(Q, (size_t)ldq * sizeof(double), v.Q, (size_t)ctx->lda * sizeof(double), (size_t)ctx->n * sizeof(double),
-                                  (size_t)rows, hipMemcpyDeviceToHost, ctx->stream));
+    CGX_TRY(download_columns(ctx, Q, ldq, v.Q, (size_t)rows));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int t = 0; t < steps; ++t) {
         alpha[t] = t < m ? a[(size_t)t] : 0.0;
@@ -293,8 +260,7 @@ cgx_status cgx_probe_eigs_basis(cgx_ctx *ctx, int steps, const double *v0, doubl
 cgx_status cgx_probe_eigs_orthogonalise(cgx_ctx *ctx, int nslots, const double *Q, long ldq, const double *w_in, double *w_out, double *h_out)
 {
     const std::string name("cgx_probe_eigs_orthogonalise");
-    CGX_TRY(check_one_gpu_call(ctx, name));
-    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, name + ": dense storage only (CGX_MATRIX_DENSE)");
+    CGX_TRY(check_dense_one_gpu(ctx, name));
     if (nslots < 1 || nslots > CGX_MAX_LANCZOS_STEPS || !Q || !w_in || !w_out || !h_out || ldq < ctx->n)
         return fail(ctx, CGX_ERR_BAD_ARG, name + ": bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -306,7 +272,7 @@ cgx_status cgx_probe_eigs_orthogonalise(cgx_ctx *ctx, int nslots, const double *
     hs.m = cgx::kEigsLive;
     HIP_TRY(ctx, hipMemsetAsync(v.Q, 0xFF, ((size_t)nslots + 1) * pitch, st));
     HIP_TRY(ctx, hipMemsetAsync(v.W, 0xFF, pitch, st));
-    HIP_TRY(ctx, hipMemcpy2DAsync(v.Q, pitch, Q, (size_t)ldq * sizeof(double), row, (size_t)nslots, hipMemcpyHostToDevice, st));
+    CGX_TRY(upload_columns(ctx, v.Q, Q, ldq, (size_t)nslots));
     HIP_TRY(ctx, hipMemcpyAsync(v.W, w_in, row, hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(v.sc, &hs, sizeof hs, hipMemcpyHostToDevice, st));
     const cgx::EigsArgs a = step_args(ctx, v, nslots - 1);

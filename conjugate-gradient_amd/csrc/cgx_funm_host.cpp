@@ -2,9 +2,9 @@
 //
 // One GPU, dense storage, no preconditioner.  The recurrence is cgx_lanczos's own (lanczos_run, cgx_lanczos_host.cpp) with one
 // device-to-device copy behind every step that keeps the normalised v_t; one synchronisation ends it.  The coefficients
-// ||b_j|| f(T_j) e_1 and the lagged ones behind change[] are made on the host (tridiag_function, O(m^2) per column), go up with the
-// step counts, and one launch of k_funm_combine (cgx_funm.hip) sums the basis.  The table, the step counts, the result block and the
-// basis live in ONE device allocation of the context (cgx_ctx::funm), apart from every other path's buffers.
+// ||b_j|| f(T_j) e_1 and the lagged ones behind change[] are made on the host (tridiag_function, cgx_tridiag.cpp: O(m^2) per
+// column), go up with the step counts, and one launch of k_funm_combine (cgx_funm.hip) sums the basis.  The table, the step counts,
+// the result block and the basis live in ONE device allocation of the context (cgx_ctx::funm), apart from every other path's buffers.
 #include "cgx_internal.h"
 
 #include <cmath>
@@ -40,18 +40,9 @@ size_t funm_layout(const cgx_ctx *ctx, double *base, int nvec, int steps, FunmVi
 // The block for a call of (nvec, steps): made on first use, made again when this call needs more than it holds.
 cgx_status ensure_funm(cgx_ctx *ctx, const std::string &fn, int nvec, int steps, FunmView *v)
 {
-    const size_t bytes = funm_layout(ctx, nullptr, nvec, steps, v);
-    if (ctx->funm && ctx->funm_bytes < bytes) {
-        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-        (void)hipFree(ctx->funm);
-        ctx->funm = nullptr;
-        ctx->funm_bytes = 0;
-    }
-    const cgx_status st = ensure_side_block(ctx, &ctx->funm, &ctx->funm_bytes, bytes);
-    if (st == CGX_ERR_OOM)
-        return fail(ctx, CGX_ERR_OOM, fn + ": no device memory for the Lanczos basis: " + std::to_string(bytes) + " bytes (8 steps nvec lda = " +
-                                          std::to_string(steps) + " x " + std::to_string(nvec) + " x " + std::to_string(ctx->lda) + " doubles)");
-    CGX_TRY(st);
+    CGX_TRY(ensure_growing_block(ctx, &ctx->funm, &ctx->funm_bytes, funm_layout(ctx, nullptr, nvec, steps, v), fn,
+                                 "8 steps nvec lda = " + std::to_string(steps) + " x " + std::to_string(nvec) + " x " +
+                                     std::to_string(ctx->lda) + " doubles"));
     funm_layout(ctx, ctx->funm, nvec, steps, v);
     return CGX_OK;
 }
@@ -59,11 +50,10 @@ cgx_status ensure_funm(cgx_ctx *ctx, const std::string &fn, int nvec, int steps,
 cgx_status run_combine(cgx_ctx *ctx, const FunmView &v, int nvec, int steps, const double *coef, const int *m, double *X, long ldx)
 {
     hipStream_t st = ctx->stream;
-    const int n = ctx->n;
     HIP_TRY(ctx, hipMemcpyAsync(v.C, coef, (size_t)nvec * steps * sizeof(double), hipMemcpyHostToDevice, st));
     HIP_TRY(ctx, hipMemcpyAsync(v.m, m, (size_t)nvec * sizeof(int), hipMemcpyHostToDevice, st));
     cgx::FunmArgs a{};
-    a.n = n;
+    a.n = ctx->n;
     a.nvec = nvec;
     a.steps = steps;
     a.lda = ctx->lda;
@@ -73,8 +63,7 @@ cgx_status run_combine(cgx_ctx *ctx, const FunmView &v, int nvec, int steps, con
     a.X = v.X;
     a.ldx = ctx->lda;
     HIP_TRY(ctx, cgx::launch_funm_combine(a, st));
-    HIP_TRY(ctx, hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), v.X, (size_t)ctx->lda * sizeof(double), (size_t)n * sizeof(double), nvec,
-                                  hipMemcpyDeviceToHost, st));
+    CGX_TRY(download_columns(ctx, X, ldx, v.X, nvec));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return CGX_OK;
 }
@@ -91,9 +80,7 @@ struct ColumnCoef {
 ColumnCoef column_coefficients(int m, const double *a, const double *b, int fn, double param, double z2, double *cj)
 {
     ColumnCoef out;
-    bool finite = m >= 1;
-    for (int t = 0; t < m && finite; ++t) finite = std::isfinite(a[t]) && (t + 1 >= m || std::isfinite(b[t]));
-    if (!finite) {
+    if (m < 1 || !finite_entries(m, a, b)) {
         out.status = TridiagFn::no_convergence;
         return out;
     }
@@ -124,7 +111,7 @@ cgx_status cgx_apply_function(cgx_ctx *ctx, int fn, double param, int nvec, int 
                               int *steps_done, double *change, double *coef)
 {
     const std::string name("cgx_apply_function");
-    CGX_TRY(check_lanczos(ctx, "cgx_apply_function", steps));
+    CGX_TRY(check_lanczos(ctx, name, steps));
     if (nvec < 1 || nvec > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, name + ": nvec must be 1 .. CGX_MAX_RHS");
     if (!B || !X) return fail(ctx, CGX_ERR_BAD_ARG, name + ": null pointer");
     if (ldb < ctx->n || ldx < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, name + ": leading dimension smaller than n");
@@ -137,7 +124,7 @@ cgx_status cgx_apply_function(cgx_ctx *ctx, int fn, double param, int nvec, int 
     std::vector<double> alpha((size_t)nvec * steps), beta((size_t)nvec * steps), c((size_t)nvec * steps, 0.0);
     int m[kW];
     double z2[kW];
-    CGX_TRY(lanczos_run(ctx, "cgx_apply_function", nvec, steps, B, ldb, 0, alpha.data(), beta.data(), m, z2, v.Q));
+    CGX_TRY(lanczos_run(ctx, name, false, nvec, steps, B, ldb, 0, alpha.data(), beta.data(), m, z2, v.Q));
     // The columns' coefficients are independent of each other: above kThreadedSteps steps (two O(m^2) sweeps per column, some
     // milliseconds at 256 steps) every column gets a host thread of its own.  The refusals are then made in column order.
     ColumnCoef col[kW];
@@ -183,8 +170,7 @@ cgx_status cgx_probe_funm_combine(cgx_ctx *ctx, int nvec, int steps, const int *
                                   long ldx)
 {
     const std::string name("cgx_probe_funm_combine");
-    CGX_TRY(check_one_gpu_call(ctx, name));
-    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, name + ": dense storage only (CGX_MATRIX_DENSE)");
+    CGX_TRY(check_dense_one_gpu(ctx, name));
     if (nvec < 1 || nvec > CGX_MAX_RHS || steps < 1 || steps > CGX_MAX_LANCZOS_STEPS || !m || !Q || !C || !X || ldq < ctx->n || ldx < ctx->n)
         return fail(ctx, CGX_ERR_BAD_ARG, name + ": bad argument");
     for (int j = 0; j < nvec; ++j)
@@ -192,8 +178,7 @@ cgx_status cgx_probe_funm_combine(cgx_ctx *ctx, int nvec, int steps, const int *
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     FunmView v;
     CGX_TRY(ensure_funm(ctx, name, nvec, steps, &v));
-    HIP_TRY(ctx, hipMemcpy2DAsync(v.Q, (size_t)ctx->lda * sizeof(double), Q, (size_t)ldq * sizeof(double), (size_t)ctx->n * sizeof(double),
-                                  (size_t)steps * nvec, hipMemcpyHostToDevice, ctx->stream));
+    CGX_TRY(upload_columns(ctx, v.Q, Q, ldq, (size_t)steps * nvec));
     return run_combine(ctx, v, nvec, steps, C, m, X, ldx);
 }
 

@@ -7,11 +7,13 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <functional>
 #include <string>
 #include <vector>
 
 #include "cgx_kernels.h"
 #include "cgx_rccl.h"
+#include "cgx_tridiag.h"
 
 namespace cgxi {
 
@@ -333,6 +335,10 @@ int default_parse_threads();   // CGX_MTX_THREADS, else the host's hardware thre
 cgx_status prepare_jacobi(cgx_ctx *ctx);   // inside cgx_solve_begin: refusals, buffers, and once per matrix dinv or the block inverses
 cgx_status prepare_lowrank(cgx_ctx *ctx);  // the same for CGX_PRECOND_PIVCHOL: once per matrix, rank and shift the factor
 cgx::LrWork lr_work(const cgx_ctx *ctx);   // the pieces of ctx->lr_block (null pointers before the first prepare_lowrank)
+// The preconditioner of a multi-vector call (cgx_solve_multi_pc, the preconditioned Lanczos calls), behind the argument checks: the
+// refusals of the single path's set-up with their status and message, block Jacobi refused, and -- once per matrix (rank, shift) --
+// the inverse diagonal or the factor, by the two functions above.
+cgx_status prepare_multi_precond(cgx_ctx *ctx, const std::string &fn);
 
 // cgx_solve.cpp: the exchanges, one iteration, the persistent launches
 cgx_status p2p_allgather(cgx_ctx *ctx, int chan, const double *src, int count, double *dst, long dst_stride, int copy_self,
@@ -356,16 +362,73 @@ cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn);
 // A side block of the context (cgx_ctx::multi, cgx_ctx::shift): allocated and zeroed on first use, freed again if that fails.
 cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes);
 
-// cgx_lanczos_host.cpp: what cgx_apply_function (cgx_funm_host.cpp) shares with cgx_lanczos and the Gauss rule
-cgx_status check_lanczos(cgx_ctx *ctx, const char *name, int steps);
-cgx_status lanczos_run(cgx_ctx *ctx, const char *name, int nvec, int steps, const double *V0, long ldv, int col0, double *alpha,
-                       double *beta, int *m, double *z2, double *basis = nullptr);
-bool funm_args_ok(int fn, double param);   // a known CGX_FN_*, and for CGX_FN_EXP a finite param >= 0
-enum class TridiagFn { ok, no_convergence, domain };
-TridiagFn tridiag_function(int m, const double *alpha, const double *beta, int fn, double param, double *coef, double *minmax, double *bad);
-// ... and with cgx_eigenpairs (cgx_eigs_host.cpp): all eigenvalues ascending into theta (may be null) and the unit eigenvectors of
-// index[0 .. nsel) as rows of S (m doubles each, first component >= 0); false: no convergence
-bool tridiag_eigenvectors(int m, const double *alpha, const double *beta, int nsel, const int *index, double *theta, double *S);
+// ... and one that grows (cgx_ctx::funm, cgx_ctx::eigs): made on first use, made again when a call needs more than it holds.
+// detail: what the out-of-memory message says the bytes are for.
+cgx_status ensure_growing_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes, const std::string &fn,
+                                const std::string &detail);
+// check_one_gpu_call, then dense storage
+cgx_status check_dense_one_gpu(cgx_ctx *ctx, const std::string &fn);
+
+// host rows (one vector per row, pitch ld) <-> a device block (column j at + j * lda); rows 0 .. n-1 only
+inline cgx_status upload_columns(cgx_ctx *ctx, double *dst, const double *src, long ld, size_t ncol)
+{
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ctx->lda * sizeof(double), src, (size_t)ld * sizeof(double),
+                                  (size_t)ctx->n * sizeof(double), ncol, hipMemcpyHostToDevice, ctx->stream));
+    return CGX_OK;
+}
+
+inline cgx_status download_columns(cgx_ctx *ctx, double *dst, long ld, const double *src, size_t ncol)
+{
+    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ld * sizeof(double), src, (size_t)ctx->lda * sizeof(double),
+                                  (size_t)ctx->n * sizeof(double), ncol, hipMemcpyDeviceToHost, ctx->stream));
+    return CGX_OK;
+}
+
+// What the plain multi-vector K1 (launch_multi_gemv, fused = false) takes on one GPU: Y = A v for nrhs columns and the v.Av partials
+inline cgx::MultiArgs plain_k1m_args(const cgx_ctx *ctx, int nrhs, const double *v, double *Y, double *partials)
+{
+    cgx::MultiArgs g{};
+    g.A = ctx->shards[0].A;
+    g.lda = ctx->lda;
+    g.n = ctx->n;
+    g.nrhs = nrhs;
+    g.v = v;
+    g.Y = Y;
+    g.partials = partials;
+    return g;
+}
+
+// cgx_lanczos_host.cpp: what the Lanczos family shares (DESIGN.md sections 17 - 20)
+cgx_status check_lanczos_steps(cgx_ctx *ctx, const std::string &fn, int steps);
+// check_dense_one_gpu, "a preconditioner is set and would be ignored", check_lanczos_steps: every call on the plain recurrence
+cgx_status check_lanczos(cgx_ctx *ctx, const std::string &fn, int steps);
+// The side block of a recurrence: cgx_ctx::lanczos, or, pc, cgx_ctx::lanczos_pc, which alone has the pieces U and tpart.
+struct LanczosView {
+    double *V[2], *U, *Y;           // kMaxRhs x lda each (column j at + j * lda): w / v_prev in ping-pong, u = M^-1 w, K1m's product
+    double *k1p;                    // kMaxRhs x k1p_stride(n): K1m's partials
+    double *wwp[2];                 // kMaxRhs x multi_update_grid(n) each: the ||w||^2 (pc: w.u) partials, ping-pong over the steps
+    double *tpart;                  // kMaxRhs x lr_grid(n) x kLrLd: the partials of L^T w (pivoted Cholesky)
+    double *alpha, *beta;           // kMaxRhs x kMaxLanczosSteps each: the histories
+    cgx::LanczosScalars *ls;
+};
+cgx_status lanczos_block(cgx_ctx *ctx, bool pc, LanczosView *v);   // made on first use
+// THE recurrence: nvec start vectors through `steps` steps, plain or, pc, with the context's prepared preconditioner.  V0 (one
+// vector per row, pitch ldv) is uploaded, or, V0 == nullptr, the block V[0] is taken as the caller left it on the device.  alpha,
+// beta: nvec rows of `steps` doubles, zero at t >= m[j]; z2[j] = ||V0_j||^2 (pc: eta0^2 = V0_j . M^-1 V0_j) as the device summed
+// it.  col0: the number of row 0 in the caller's own count, for the message about a bad start vector.  basis != nullptr
+// (cgx_apply_function): behind step t the block that now holds the normalised v_t is copied into slot t, nvec * lda doubles each.
+cgx_status lanczos_run(cgx_ctx *ctx, const std::string &fn, bool pc, int nvec, int steps, const double *V0, long ldv, int col0,
+                       double *alpha, double *beta, int *m, double *z2, double *basis = nullptr);
+// THE stochastic Lanczos quadrature on that recurrence: the mean over nprobe probes of z2 sum_i weight_i f(theta_i), its standard
+// error, the values per probe and the extreme Ritz values (the last two may be null).  The probes are the rows of Z, or, Z == nullptr,
+// what device_probes(probe0, nb) leaves in V[0] of the recurrence's block, or, without one, the library's Rademacher signs of `seed`
+// made on the host.
+using SlqProbes = std::function<cgx_status(int probe0, int nb)>;
+cgx_status check_slq_args(cgx_ctx *ctx, const std::string &fn, int fn_kind, int nprobe, const double *estimate, const double *std_error,
+                          const double *Z, long ldz);
+cgx_status slq_estimate(cgx_ctx *ctx, const std::string &fn, bool pc, int fn_kind, int nprobe, int steps, unsigned long long seed,
+                        const double *Z, long ldz, const SlqProbes &device_probes, double *estimate, double *std_error, double *per_probe,
+                        double *ritz);
 
 // Lays a side block out in 128-byte aligned pieces; base == nullptr only measures (bytes()).
 struct Carver {

@@ -247,6 +247,11 @@ __host__ __device__ inline unsigned long long hash_mix64(unsigned long long z)
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
+// The Rademacher sign of element elem of library probe `probe` (include/cgx.h): the top bit of that hash; seed_mixed = hash_mix64(seed).
+__host__ __device__ inline double rademacher_sign(unsigned long long seed_mixed, unsigned long long probe, unsigned long long elem)
+{
+    return (hash_mix64(seed_mixed ^ ((probe << 32) | elem)) >> 63) ? -1.0 : 1.0;
+}
 // symmetric: (i, j) and (j, i) give the same value.  diag != 0: A(i,i) = diag (with symmetric and diag above the spectral
 // radius ~ 2 sqrt(n/3) of the off-diagonal part the block is SPD, so that CG runs on it for hundreds of iterations).
 __host__ __device__ inline double hash_entry(unsigned long long seed_mixed, int symmetric, double diag, long i, long j)

@@ -66,8 +66,7 @@ size_t pc_layout(const cgx_ctx *ctx, double *base, PcView *v)
 cgx_status check_multi(cgx_ctx *ctx, const char *name, int nrhs, const void *in, long ldin, const void *out, long ldout)
 {
     const std::string fn(name);
-    CGX_TRY(check_one_gpu_call(ctx, fn));
-    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    CGX_TRY(check_dense_one_gpu(ctx, fn));
     if (nrhs < 1 || nrhs > CGX_MAX_RHS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nrhs must be 1 .. CGX_MAX_RHS");
     if (!in || !out) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
     if (ldin < ctx->n || ldout < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");
@@ -111,31 +110,9 @@ cgx::MultiPcArgs pc_args(const cgx_ctx *ctx, const PcView &pv)
 
 cgx::MultiArgs plain_args(cgx_ctx *ctx, const MultiView &v, int nrhs, const double *vec)
 {
-    cgx::MultiArgs g{};
-    g.A = ctx->shards[0].A;
-    g.lda = ctx->lda;
-    g.n = ctx->n;
-    g.nrhs = nrhs;
-    g.v = vec;
-    g.Y = v.Y;
-    g.partials = v.k1p;
+    cgx::MultiArgs g = plain_k1m_args(ctx, nrhs, vec, v.Y, v.k1p);
     g.ms = v.ms;
     return g;
-}
-
-// host rows (one vector per row, pitch ld) <-> a device block (column j at + j * lda); rows 0 .. n-1 only
-cgx_status upload(cgx_ctx *ctx, double *dst, const double *src, long ld, int nrhs)
-{
-    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ctx->lda * sizeof(double), src, (size_t)ld * sizeof(double),
-                                  (size_t)ctx->n * sizeof(double), nrhs, hipMemcpyHostToDevice, ctx->stream));
-    return CGX_OK;
-}
-
-cgx_status download(cgx_ctx *ctx, double *dst, long ld, const double *src, int nrhs)
-{
-    HIP_TRY(ctx, hipMemcpy2DAsync(dst, (size_t)ld * sizeof(double), src, (size_t)ctx->lda * sizeof(double),
-                                  (size_t)ctx->n * sizeof(double), nrhs, hipMemcpyDeviceToHost, ctx->stream));
-    return CGX_OK;
 }
 
 // K1m fused of iteration k, event-timed where next_gemv_events says so (as run_gemv_fused, cgx_solve.cpp); pc: the preconditioned
@@ -153,20 +130,6 @@ cgx_status run_multi_fused(cgx_ctx *ctx, const MultiView &v, int nrhs, int k, co
     if (pc) HIP_TRY(ctx, cgx::launch_multi_gemv_pc(g, *pc, ctx->stream, e0, e1));
     else HIP_TRY(ctx, cgx::launch_multi_gemv(g, true, ctx->stream, e0, e1));
     return CGX_OK;
-}
-
-// The preconditioner of a preconditioned multi call, behind check_multi: the refusals of the single path's set-up with their status
-// and message, and -- once per matrix (rank, shift) -- the inverse diagonal or the factor, by the single path's own functions.
-cgx_status prepare_multi_pc(cgx_ctx *ctx, const char *name)
-{
-    if (ctx->precond == CGX_PRECOND_JACOBI) {
-        if (ctx->precond_block > 1)
-            return fail(ctx, CGX_ERR_UNSUPPORTED, std::string(name) + ": block Jacobi (cgx_set_preconditioner_block > 1) has no multi-vector "
-                                                                     "update kernel; point Jacobi and CGX_PRECOND_PIVCHOL have");
-        return prepare_jacobi(ctx);
-    }
-    if (ctx->precond == CGX_PRECOND_PIVCHOL) return prepare_lowrank(ctx);
-    return fail(ctx, CGX_ERR_UNSUPPORTED, std::string(name) + ": unknown preconditioner");
 }
 
 // THE multi solve: set-up, the polled loop, the final product and the results.  pre: every column runs the recurrence of DESIGN.md
@@ -190,8 +153,8 @@ cgx_status solve_multi_body(cgx_ctx *ctx, bool pre, int nrhs, const double *B, l
     const double t_begin = wall_now();
 
     // set-up, cg.cc:49-92 per column: r = b - A x0, p_old = 0, the r.r partials of iteration 0's head (pre: z0 and its partials)
-    CGX_TRY(upload(ctx, v.B, B, ldb, nrhs));
-    CGX_TRY(upload(ctx, v.X, X, ldx, nrhs));
+    CGX_TRY(upload_columns(ctx, v.B, B, ldb, nrhs));
+    CGX_TRY(upload_columns(ctx, v.X, X, ldx, nrhs));
     HIP_TRY(ctx, hipMemsetAsync(v.ms, 0, sizeof(cgx::MultiScalars), st));
     if (pre) HIP_TRY(ctx, hipMemsetAsync(pv.mp, 0, sizeof(cgx::MultiPcScalars), st));
     HIP_TRY(ctx, hipMemsetAsync(v.P[0], 0, (size_t)nrhs * lda * sizeof(double), st));
@@ -222,7 +185,7 @@ cgx_status solve_multi_body(cgx_ctx *ctx, bool pre, int nrhs, const double *B, l
     cgx::MultiPcScalars hp;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ms, sizeof hs, hipMemcpyDeviceToHost, st));
     if (pre) HIP_TRY(ctx, hipMemcpyAsync(&hp, pv.mp, sizeof hp, hipMemcpyDeviceToHost, st));
-    CGX_TRY(download(ctx, X, ldx, v.X, nrhs));
+    CGX_TRY(download_columns(ctx, X, ldx, v.X, nrhs));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
 
@@ -268,7 +231,7 @@ cgx_status cgx_solve_multi_pc(cgx_ctx *ctx, int nrhs, const double *B, long ldb,
     CGX_TRY(check_multi(ctx, "cgx_solve_multi_pc", nrhs, B, ldb, X, ldx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     const bool pre = ctx->precond != CGX_PRECOND_NONE;
-    if (pre) CGX_TRY(prepare_multi_pc(ctx, "cgx_solve_multi_pc"));
+    if (pre) CGX_TRY(prepare_multi_precond(ctx, "cgx_solve_multi_pc"));
     return solve_multi_body(ctx, pre, nrhs, B, ldb, X, ldx, res);
 }
 
@@ -279,16 +242,16 @@ cgx_status cgx_probe_multi_pc_apply(cgx_ctx *ctx, int nrhs, const double *R, lon
     CGX_TRY(check_multi(ctx, "cgx_probe_multi_pc_apply", nrhs, R, ldr, Z, ldz));
     if (ctx->precond == CGX_PRECOND_NONE) return fail(ctx, CGX_ERR_BAD_ARG, "cgx_probe_multi_pc_apply: no preconditioner is set");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    CGX_TRY(prepare_multi_pc(ctx, "cgx_probe_multi_pc_apply"));
+    CGX_TRY(prepare_multi_precond(ctx, "cgx_probe_multi_pc_apply"));
     MultiView v;
     PcView pv{};
     CGX_TRY(ensure_multi(ctx, &v));
     CGX_TRY(ensure_multi_pc(ctx, &pv));
     const cgx::MultiPcArgs pc = pc_args(ctx, pv);
-    CGX_TRY(upload(ctx, v.R, R, ldr, nrhs));
+    CGX_TRY(upload_columns(ctx, v.R, R, ldr, nrhs));
     HIP_TRY(ctx, cgx::launch_multi_update_pc(ctx->n, ctx->lda, nrhs, nullptr, nullptr, nullptr, 0, nullptr, v.R, v.rrp, v.ms, 0, pc, true,
                                              ctx->stream));
-    CGX_TRY(download(ctx, Z, ldz, pv.Z, nrhs));
+    CGX_TRY(download_columns(ctx, Z, ldz, pv.Z, nrhs));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return CGX_OK;
 }
@@ -301,11 +264,11 @@ cgx_status cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long ld
     MultiView v;
     CGX_TRY(ensure_multi(ctx, &v));
     const int g1 = cgx::multi_gemv_grid(ctx->n, cgx::multi_width(nrhs));
-    CGX_TRY(upload(ctx, v.P[0], P, ldp, nrhs));
+    CGX_TRY(upload_columns(ctx, v.P[0], P, ldp, nrhs));
     HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.P[0]), false, ctx->stream));
     std::vector<double> parts((size_t)nrhs * g1);
     HIP_TRY(ctx, hipMemcpyAsync(parts.data(), v.k1p, parts.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    CGX_TRY(download(ctx, Y, ldy, v.Y, nrhs));
+    CGX_TRY(download_columns(ctx, Y, ldy, v.Y, nrhs));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int j = 0; j < nrhs; ++j) {   // the workgroups' partials in ascending order
         double s = 0.0;

@@ -272,4 +272,16 @@ cgx_status prepare_lowrank(cgx_ctx *ctx)
     return CGX_OK;
 }
 
+cgx_status prepare_multi_precond(cgx_ctx *ctx, const std::string &fn)
+{
+    if (ctx->precond == CGX_PRECOND_JACOBI) {
+        if (ctx->precond_block > 1)
+            return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": block Jacobi (cgx_set_preconditioner_block > 1) has no multi-vector update kernel; "
+                                                       "point Jacobi and CGX_PRECOND_PIVCHOL have");
+        return prepare_jacobi(ctx);
+    }
+    if (ctx->precond == CGX_PRECOND_PIVCHOL) return prepare_lowrank(ctx);
+    return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": unknown preconditioner");
+}
+
 }  // namespace cgxi

@@ -135,23 +135,16 @@ cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, doub
             HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, lda, v.X + (size_t)j * lda, v.Y + (size_t)j * lda,
                                                     s.k1_part(), st));
     } else {
-        cgx::MultiArgs g{};
-        g.A = s.A;
-        g.lda = lda;
-        g.n = n;
-        g.nrhs = kS;   // always the full width: a row's sum order depends on the kernel width, and a shift's result must not
-                       // depend on how many others there are (the columns beyond nshift hold zeros or an earlier call's x)
-        g.v = v.X;
-        g.Y = v.Y;
-        g.partials = v.k1p;
+        // always the full width kS: a row's sum order depends on the kernel width, and a shift's result must not depend on how many
+        // others there are (the columns beyond nshift hold zeros or an earlier call's x)
+        cgx::MultiArgs g = plain_k1m_args(ctx, kS, v.X, v.Y, v.k1p);
         g.ms = v.ms;
         HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
     }
     HIP_TRY(ctx, cgx::launch_shift_norms(n, lda, nshift, v.Y, s.b_full, v.X, v.ss, st));
     cgx::ShiftScalars hs;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ss, sizeof hs, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpy2DAsync(X, (size_t)ldx * sizeof(double), v.X, (size_t)lda * sizeof(double), (size_t)n * sizeof(double), nshift,
-                                  hipMemcpyDeviceToHost, st));
+    CGX_TRY(download_columns(ctx, X, ldx, v.X, nshift));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
 

@@ -575,6 +575,13 @@ cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn)
     return CGX_OK;
 }
 
+cgx_status check_dense_one_gpu(cgx_ctx *ctx, const std::string &fn)
+{
+    CGX_TRY(check_one_gpu_call(ctx, fn));
+    if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    return CGX_OK;
+}
+
 // (zeroed: the pad rows of every vector in the block stay 0)
 cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes)
 {
@@ -592,6 +599,21 @@ cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, 
     *block = p;
     *block_bytes = bytes;
     return CGX_OK;
+}
+
+cgx_status ensure_growing_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes, const std::string &fn,
+                                const std::string &detail)
+{
+    if (*block && *block_bytes < bytes) {
+        HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+        (void)hipFree(*block);
+        *block = nullptr;
+        *block_bytes = 0;
+    }
+    const cgx_status st = ensure_side_block(ctx, block, block_bytes, bytes);
+    if (st == CGX_ERR_OOM)
+        return fail(ctx, CGX_ERR_OOM, fn + ": no device memory for the Lanczos basis: " + std::to_string(bytes) + " bytes (" + detail + ")");
+    return st;
 }
 
 // What cgx_solve_end reports apart from the K1 timing.  rr: r.r of the last two iterations by parity; sums: |A x - b|^2, |b|^2, |x|^2

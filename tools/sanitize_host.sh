@@ -2,7 +2,8 @@
 # Sanitizers on the HOST code, CPU only (GPU AddressSanitizer is not available on this pool): the library's host translation
 # units built with clang's AddressSanitizer + UndefinedBehaviorSanitizer and, separately, ThreadSanitizer, and driven through
 # the host-only entry point of the Matrix-Market parser on edge-case files (a file ending exactly at a page boundary, short
-# files, bad tokens, over-long tokens, no entries, forced thread counts from 1 to 33); and the cgsolver CLI with ASan through
+# files, bad tokens, over-long tokens, no entries, forced thread counts from 1 to 33); the Jacobi-matrix code of the Lanczos family
+# (csrc/cgx_tridiag.cpp) under the same two settings through tools/sanitize/tridiag_harness.cc; and the cgsolver CLI with ASan through
 # its no-GPU paths (usage, --cpu, no device, a rank that never answers).  Prints every sanitizer report; exit code 1 if any.
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
@@ -39,6 +40,12 @@ for san in "address,undefined" "thread"; do
   ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1 TSAN_OPTIONS=report_signal_unsafe=0 ./harness_${san%%,*} $FILES > out_${san%%,*}.txt 2>&1 || true
   if grep -E "ERROR: AddressSanitizer|runtime error:|WARNING: ThreadSanitizer" out_${san%%,*}.txt; then fail=1; fi
   echo "$san: $(grep -c 'status' out_${san%%,*}.txt) parser calls, $(grep -cE 'ERROR: AddressSanitizer|runtime error:|WARNING: ThreadSanitizer' out_${san%%,*}.txt) sanitizer reports"
+  # the Jacobi-matrix code (csrc/cgx_tridiag.cpp: host arithmetic only, so it links by itself) through its three public functions,
+  # the last of them from 15 threads at once as cgx_apply_function runs it
+  $CL -fsanitize=$san -fno-omit-frame-pointer -g -O1 -std=c++17 -I$R/include $R/tools/sanitize/tridiag_harness.cc $P/csrc/cgx_tridiag.cpp -o tridiag_${san%%,*} -lpthread
+  ASAN_OPTIONS=detect_leaks=0 UBSAN_OPTIONS=print_stacktrace=1 ./tridiag_${san%%,*} > tri_${san%%,*}.txt 2>&1 || { fail=1; grep UNEXPECTED tri_${san%%,*}.txt || tail -5 tri_${san%%,*}.txt; }
+  if grep -E "ERROR: AddressSanitizer|runtime error:|WARNING: ThreadSanitizer" tri_${san%%,*}.txt; then fail=1; fi
+  echo "$san: $(grep -c 'status' tri_${san%%,*}.txt) tridiagonal calls, $(grep -cE 'ERROR: AddressSanitizer|runtime error:|WARNING: ThreadSanitizer' tri_${san%%,*}.txt) sanitizer reports"
 done
 # the CLI through its no-GPU paths (libcgx.so itself is not instrumented)
 g++ -fsanitize=address,undefined -g -O1 -std=c++17 -pthread -I$R/include -o cgsolver_asan $P/host/cg.cc $P/host/cg_main.cc -L$P -lcgx -Wl,-rpath,$P -Wl,-rpath,/opt/rocm/lib
