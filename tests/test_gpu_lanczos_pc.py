@@ -99,7 +99,8 @@ def _check_coefficients(tag, n, got, refs, nvec):
 
 # ---- 1. the coefficients ----------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("n,rank,nvec", [(1000, 64, 1), (1000, 64, 3), (1000, 64, 8), (1000, 64, 16), (1000, 16, 1), (1000, 16, 3),
-                                         (1000, 16, 8), (1000, 16, 16), (1000, 5, 3), (257, 5, 3)])
+                                         (1000, 16, 8), (1000, 16, 16), (1000, 5, 3), (257, 5, 3), (1000, 64, 2), (1000, 64, 5),
+                                         (1000, 64, 9)])
 def test_coefficients_pivchol(gpu_pkg, n, rank, nvec):
     A, V0 = _kernel(n), _start_vectors(n)
     with _kernel_solver(gpu_pkg, n, rank) as s:

@@ -99,7 +99,7 @@ def test_fixed_iterations_pivchol(gpu_pkg, n, rank):
     with _kernel_solver(gpu_pkg, n, rank) as s:
         s.set_max_iter(iters)
         s.tolerance(0.0)
-        for k in (1, 3, 8, 16):
+        for k in (1, 2, 3, 5, 8, 9, 16):
             out[k] = s.solve_multi_pc(B[:k], X0[:k])
         _, L, delta = s._probe_precond_lowrank()
     r64, rld = _references(("fix", n, rank), A, B, X0, (ref.Woodbury(L, delta, np.float64).apply, ref.Woodbury(L, delta, ref.LD).apply),
@@ -265,7 +265,7 @@ def test_apply_matches_the_single_path(gpu_pkg, n, rank):
         s.tolerance(0.0)
         s.solve_multi_pc(R[:3])                           # the multi call makes the factor ...
         single = np.array([s._probe_precond_apply(R[j]) for j in range(16)])   # ... the single path's kernels use it
-        for k in (1, 3, 8, 16):
+        for k in (1, 2, 3, 5, 8, 9, 16):
             Z = s._probe_multi_pc_apply(R[:k])
             assert np.all(np.isfinite(Z)) and np.linalg.norm(Z) > 0
             assert np.array_equal(Z.view(np.uint64), single[:k].view(np.uint64)), (k, float(np.abs(Z - single[:k]).max()))
