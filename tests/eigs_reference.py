@@ -13,7 +13,7 @@ POLL = 16                  # tol > 0: the Ritz estimates are looked at behind ev
 def lanczos_reorth_f64(A, v0, steps):
     """(alpha, beta, m, Q): alpha, beta of length `steps` with zeros at t >= m; Q has steps + 1 rows: q_0 .. q_(m-1) and, when the
     run was not frozen, q_m; the rows behind them are zero."""
-    A = np.asarray(A, dtype=np.float64)
+    A = ref.as_matrix(A, np.float64)                         # an array as before; a matrix-free operator as it is
     n = A.shape[0]
     alpha, beta = np.zeros(steps), np.zeros(steps)
     v0 = np.asarray(v0, dtype=np.float64)
@@ -58,7 +58,7 @@ def ritz(alpha, beta, m, which, nev):
 def eigenpairs_f64(A, v0, which, nev, steps, tol=0.0, run=None):
     """cgx_eigenpairs restated: (values, vectors, info) with info = dict(residual, estimate, steps_done, nfound, alpha, beta).
     run: a kept lanczos_reorth_f64(A, v0, steps) result (the prefix property makes a shorter run its leading part)."""
-    A = np.asarray(A, dtype=np.float64)
+    A = ref.as_matrix(A, np.float64)                         # an array as before; a matrix-free operator as it is
     n = A.shape[0]
     alpha, beta, m_full, Q = run if run is not None else lanczos_reorth_f64(A, v0, steps)
     m = m_full

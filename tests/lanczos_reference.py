@@ -1,6 +1,7 @@
 """Host restatements for the Lanczos quadrature tests (tests/test_lanczos_abi.py, tests/test_gpu_lanczos.py): the recurrence of
 csrc/cgx_lanczos.hip in float64 numpy, a longdouble Lanczos with full reorthogonalisation as the high-precision reference, Gauss
-quadrature through numpy.linalg.eigh of the dense Jacobi matrix, the library's Rademacher probes, and the tolerance rule."""
+quadrature through numpy.linalg.eigh of the dense Jacobi matrix, the library's Rademacher probes, the tolerance rule, and a
+matrix-free generate_lap2d_matrix for the sizes of tests/test_gpu_lanczos_tiles.py (the restatements need only A @ x)."""
 import numpy as np
 
 BREAK = 2.0 ** -36   # beta_t <= BREAK * max |alpha|: the column is frozen (include/cgx.h cgx_lanczos)
@@ -35,9 +36,58 @@ def lanczos_f64(A, v0, steps):
     return alpha, beta, m
 
 
+class Lap2dOperator:
+    """generate_lap2d_matrix(n) without the n x n array, for the sizes at which a dense longdouble reference costs too much: the
+    non-zeros of oracle.generate_lap2d(n, row0, nrows), taken `chunk` rows at a time and kept per row, padded to the longest row
+    with zeros on the row's own diagonal.  A @ x for x of shape (n,) or (n, k) in float64 or longdouble, the dtype following x
+    (anything else is taken as float64); every row is summed in ascending column order.  tests/test_lap2d_operator.py compares it
+    with the dense matrix."""
+    __array_ufunc__ = None   # ndarray @ operator is refused, not broadcast over the object
+
+    def __init__(self, oracle, n, chunk=1024):
+        self.shape = (n, n)
+        rows, cols, vals = [], [], []
+        for r0 in range(0, n, chunk):
+            block = oracle.generate_lap2d(n, r0, min(chunk, n - r0))
+            r, c = np.nonzero(block)                          # row-major: ascending columns within a row
+            rows.append(r + r0)
+            cols.append(c)
+            vals.append(block[r, c])
+        rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+        count = np.bincount(rows, minlength=n)
+        self.nnz = int(count.sum())
+        first = np.concatenate([[0], np.cumsum(count)[:-1]])
+        k = np.arange(self.nnz) - first[rows]                 # the entry's position in its row
+        self.cols = np.repeat(np.arange(n)[:, None], int(count.max()), axis=1)
+        self.vals = np.zeros(self.cols.shape)
+        self.cols[rows, k] = cols
+        self.vals[rows, k] = vals
+
+    def __matmul__(self, x):
+        x = np.asarray(x)
+        if x.dtype != np.longdouble:
+            x = x.astype(np.float64, copy=False)
+        assert x.ndim in (1, 2) and x.shape[0] == self.shape[0], x.shape
+        vals = self.vals.astype(x.dtype, copy=False)
+        y = np.zeros(x.shape, dtype=x.dtype)
+        for k in range(self.cols.shape[1]):                   # ascending position: one fixed order per row
+            xk = x[self.cols[:, k]]
+            y += vals[:, k] * xk if x.ndim == 1 else vals[:, k, None] * xk
+        return y
+
+
+def is_operator(A):
+    return isinstance(A, Lap2dOperator)
+
+
+def as_matrix(A, dtype):
+    """np.asarray(A, dtype) for arrays; a matrix-free operator as it is (its products take the operand's dtype)."""
+    return A if is_operator(A) else np.asarray(A, dtype=dtype)
+
+
 def lanczos_longdouble(A, v0, steps):
     """Lanczos in longdouble with full reorthogonalisation (twice) against every earlier vector: (alpha, beta) of length steps."""
-    Al = np.asarray(A, dtype=np.longdouble)
+    Al = as_matrix(A, np.longdouble)
     v = np.asarray(v0, dtype=np.longdouble)
     v = v / np.sqrt(v @ v)
     V = [v]

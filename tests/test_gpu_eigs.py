@@ -10,6 +10,8 @@ The tolerance rule is that of tests/test_gpu_lanczos.py: wherever a device resul
 d_cpu, the deviation of the float64 numpy restatement of the same recurrence (tests/eigs_reference.py) from that reference, and
 allows the device 16 max(d_cpu, n 2^-52), relative to the norm of the reference (lanczos_reference.tolerance); eigenvectors are
 compared after aligning the sign.  A truncated run passes under the same rule because device and restatement share the truncation.
+
+Past 16 row tiles and at 1024 slots (n = 4096 .. 16400): tests/test_gpu_lanczos_tiles.py.
 """
 import os
 import re
@@ -88,24 +90,30 @@ def test_pass_is_exact(gpu_pkg, n, lda_pad):
     host the rows behind nslots, the columns behind n and w's tail hold NaN / inf; on the device the probe fills the slots it uses,
     the slot behind them and w with NaN over the whole row pitch before it uploads the n columns (include/cgx.h)."""
     c = gpu_pkg.cgx.EIGS_SLOT_CHUNK
+    with _dense_solver(gpu_pkg, 2.0 * np.eye(n), lda_pad=lda_pad) as s:
+        _pass_is_exact(s, n, lda_pad, (1, 2, 37, c - 1, c, c + 1, 2))   # the last one reuses the larger block
+
+
+def _pass_is_exact(s, n, lda_pad, slot_counts):
+    """The pass on the context s (any n x n matrix: the pass does not read it) for every nslots of slot_counts.  Also run by
+    tests/test_gpu_lanczos_tiles.py past 16 tiles and at 1024 slots."""
     rng = np.random.default_rng(10 * n + lda_pad + 1)
     poison = [np.nan, np.inf, -np.inf]
-    with _dense_solver(gpu_pkg, 2.0 * np.eye(n), lda_pad=lda_pad) as s:
-        for nslots in (1, 2, 37, c - 1, c, c + 1, 2):             # the last one reuses the larger block
-            Q = np.full((nslots + 2, n + 3), np.nan)
-            Q[:nslots, :n] = rng.integers(-8, 9, (nslots, n))
-            for r in range(nslots + 2):
-                Q[r, n:] = poison[r % 3]
-            Q[nslots] = np.inf
-            Q[nslots + 1] = -np.inf
-            w = np.full(n + 2, np.nan)
-            w[:n] = rng.integers(-8, 9, n)
-            want_h = Q[:nslots, :n] @ w[:n]
-            want_w = w[:n] - want_h @ Q[:nslots, :n]
-            assert np.max(np.abs(want_w)) < 2.0 ** 50
-            h, out = s._probe_eigs_orthogonalise(Q, w, nslots)
-            assert np.array_equal(h, want_h), (n, nslots, np.argwhere(h != want_h)[:4])
-            assert np.array_equal(out, want_w), (n, nslots, np.argwhere(out != want_w)[:4])
+    for nslots in slot_counts:
+        Q = np.full((nslots + 2, n + 3), np.nan)
+        Q[:nslots, :n] = rng.integers(-8, 9, (nslots, n))
+        for r in range(nslots + 2):
+            Q[r, n:] = poison[r % 3]
+        Q[nslots] = np.inf
+        Q[nslots + 1] = -np.inf
+        w = np.full(n + 2, np.nan)
+        w[:n] = rng.integers(-8, 9, n)
+        want_h = Q[:nslots, :n] @ w[:n]
+        want_w = w[:n] - want_h @ Q[:nslots, :n]
+        assert np.max(np.abs(want_w)) < 2.0 ** 50
+        h, out = s._probe_eigs_orthogonalise(Q, w, nslots)
+        assert np.array_equal(h, want_h), (n, nslots, np.argwhere(h != want_h)[:4])
+        assert np.array_equal(out, want_w), (n, nslots, np.argwhere(out != want_w)[:4])
 
 
 # ---- 2. the basis -----------------------------------------------------------------------------------------------------------------
@@ -173,8 +181,12 @@ def _check_estimates(tag, n, norm, s, v0, steps, which, nev, info):
 @pytest.mark.parametrize("which", ["largest", "smallest"])
 @pytest.mark.parametrize("steps", [300, 200])
 def test_hash_matrix_against_eigh(gpu_pkg, oracle, steps, which):
-    n, nev = 1000, 8
-    A, lam, Qe, run = _hash_case(oracle, n)
+    _hash_matrix_against_eigh(gpu_pkg, 1000, 8, steps, which, _hash_case(oracle, 1000))
+
+
+def _hash_matrix_against_eigh(gpu_pkg, n, nev, steps, which, case):
+    """case: (A, lam, Qe, run) as _hash_case makes it, run of at least `steps` steps.  (tests/test_gpu_lanczos_tiles.py: n = 4100.)"""
+    A, lam, Qe, run = case
     norm = float(np.max(np.abs(lam)))
     w = eref.LARGEST if which == "largest" else eref.SMALLEST
     cpu = eref.eigenpairs_f64(A, None, w, nev, steps, run=_cut(run, steps))
@@ -183,7 +195,7 @@ def test_hash_matrix_against_eigh(gpu_pkg, oracle, steps, which):
         got = s.eigenpairs(nev, which, steps)
         assert got[2]["steps_done"] == steps and got[2]["nfound"] == nev
         _check_estimates("hash %s %d" % (which, steps), n, norm, s, _start(n), steps, w, nev, got[2])
-    _compare("hash n=1000 %s steps=%d" % (which, steps), n, norm, got, cpu, lam_w, X_w, A)
+    _compare("hash n=%d %s steps=%d" % (n, which, steps), n, norm, got, cpu, lam_w, X_w, A)
     assert np.all(np.diff(got[0]) < 0.0) if which == "largest" else np.all(np.diff(got[0]) > 0.0)
 
 

@@ -10,6 +10,8 @@ The tolerance rule is that of tests/test_gpu_lanczos.py: wherever a device resul
 d_cpu, the deviation of the float64 numpy restatement of the same computation (tests/funm_reference.py) from that reference, and
 allows the device 16 max(d_cpu, n 2^-52), relative to the 2-norm of the reference (lanczos_reference.tolerance).  A truncated run
 passes under the same rule because device and restatement share the truncation error.
+
+Past 16 row tiles, 256 K1 partials and at 1024 steps of the combine (n = 4100): tests/test_gpu_lanczos_tiles.py.
 """
 import os
 import re
@@ -134,6 +136,11 @@ def test_exact_subspaces(gpu_pkg, nd):
 @pytest.mark.parametrize("nvec", [1, 3, 8, 16])
 @pytest.mark.parametrize("n", [257, 1000])
 def test_hash_matrix_against_eigh(gpu_pkg, oracle, n, nvec, steps):
+    _hash_matrix_against_eigh(gpu_pkg, oracle, n, nvec, steps)
+
+
+def _hash_matrix_against_eigh(gpu_pkg, oracle, n, nvec, steps):
+    """(tests/test_gpu_lanczos_tiles.py runs it at n = 4100, with its own eigen-decomposition placed in _CACHE.)"""
     A, lam, Q, B = _hash_case(oracle, n)
     runs = _hash_runs(oracle, n, steps)
     with _hash_solver(gpu_pkg, n) as s:

@@ -8,6 +8,8 @@
 The tolerance rule: wherever a device value is compared with a high-precision reference, the test computes d_cpu, the deviation of
 the float64 numpy restatement of the same recurrence (tests/lanczos_reference.py) from that reference, and allows the device
 16 max(d_cpu, n 2^-52) relative to max |alpha| or to the reference value (lanczos_reference.tolerance).
+
+Past 16 row tiles and 256 K1 partials (n = 4100 .. 16400): tests/test_gpu_lanczos_tiles.py.
 """
 import ctypes as C
 
@@ -73,7 +75,13 @@ def test_coefficients_against_longdouble(gpu_pkg, oracle, n, nvec):
     A, V0, a_ref, b_ref, a_cpu, b_cpu = _hash_case(oracle, n)
     with _hash_solver(gpu_pkg, n) as s:
         alpha, beta, done = s.lanczos(V0[:nvec], STEPS)
-    assert list(done) == [STEPS] * nvec
+    _check_coefficients(n, nvec, STEPS, alpha, beta, done, a_ref, b_ref, a_cpu, b_cpu)
+
+
+def _check_coefficients(n, nvec, steps, alpha, beta, done, a_ref, b_ref, a_cpu, b_cpu):
+    """The device's (alpha, beta, done) of `steps` steps on nvec columns against the longdouble recurrence (a_ref, b_ref) under the
+    rule, d_cpu from the float64 restatement (a_cpu, b_cpu).  Also run by tests/test_gpu_lanczos_tiles.py at n up to 16400."""
+    assert list(done) == [steps] * nvec
     for j in range(nvec):
         scale = float(np.max(np.abs(a_ref[j])))
         d_cpu = float(max(np.max(np.abs(a_cpu[j] - a_ref[j])), np.max(np.abs(b_cpu[j] - b_ref[j])))) / scale
@@ -85,7 +93,12 @@ def test_coefficients_against_longdouble(gpu_pkg, oracle, n, nvec):
 # ---- 2. breakdown and freezing ----------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("nd", [4, 8])
 def test_breakdown_and_freezing(gpu_pkg, nd):
-    n, steps = 1000, 12
+    _breakdown_and_freezing(gpu_pkg, nd, 1000)
+
+
+def _breakdown_and_freezing(gpu_pkg, nd, n):
+    """(tests/test_gpu_lanczos_tiles.py runs it at n = 4100.)"""
+    steps = 12
     A, H, d = ref.householder_matrix(n, np.linspace(1.0, 9.0, nd), 40 + nd)
     rng = np.random.default_rng(nd)
     Z = rng.choice([-1.0, 1.0], (3, n))
