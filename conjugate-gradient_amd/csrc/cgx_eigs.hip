@@ -315,13 +315,7 @@ hipError_t launch_eigs_combine(int n, long lda, int m, int nev, const double *Q,
 {
     if (n < 1 || lda < n || ldx < n || m < 1 || m > kMaxLanczosSteps || nev < 1 || nev > kMaxEigenpairs) return hipErrorInvalidValue;
     const dim3 grid((n + kCombineThreads) / kCombineThreads), block(kCombineThreads);   // rows 0 .. n: the zero behind an odd n
-    switch (multi_width(nev)) {
-    case 1: hipLaunchKernelGGL(k_eigs_combine<1>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); break;
-    case 2: hipLaunchKernelGGL(k_eigs_combine<2>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); break;
-    case 4: hipLaunchKernelGGL(k_eigs_combine<4>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); break;
-    case 8: hipLaunchKernelGGL(k_eigs_combine<8>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); break;
-    default: hipLaunchKernelGGL(k_eigs_combine<16>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); break;
-    }
+    for_multi_width(nev, [&](auto w) { hipLaunchKernelGGL(k_eigs_combine<decltype(w)::value>, grid, block, 0, s, n, lda, m, nev, Q, C, X, ldx); });
     return hipGetLastError();
 }
 

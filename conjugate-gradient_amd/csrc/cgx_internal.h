@@ -335,6 +335,9 @@ int default_parse_threads();   // CGX_MTX_THREADS, else the host's hardware thre
 cgx_status prepare_jacobi(cgx_ctx *ctx);   // inside cgx_solve_begin: refusals, buffers, and once per matrix dinv or the block inverses
 cgx_status prepare_lowrank(cgx_ctx *ctx);  // the same for CGX_PRECOND_PIVCHOL: once per matrix, rank and shift the factor
 cgx::LrWork lr_work(const cgx_ctx *ctx);   // the pieces of ctx->lr_block (null pointers before the first prepare_lowrank)
+// What the multi-column kernels take of the context's preconditioner (Jacobi or pivoted Cholesky, behind prepare_multi_precond);
+// tpart: the caller's own room for the partials of L^T r, kMaxRhs x lr_grid(n) x kLrLd doubles
+cgx::PcFactor pc_factor(const cgx_ctx *ctx, double *tpart);
 // The preconditioner of a multi-vector call (cgx_solve_multi_pc, the preconditioned Lanczos calls), behind the argument checks: the
 // refusals of the single path's set-up with their status and message, block Jacobi refused, and -- once per matrix (rank, shift) --
 // the inverse diagonal or the factor, by the two functions above.

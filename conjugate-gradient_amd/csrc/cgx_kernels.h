@@ -4,6 +4,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 namespace cgx {
 
 // Small scalar exchange of the verification phase (cg.cc:144-151): every shard publishes kSlots doubles, the
@@ -507,6 +509,18 @@ struct MultiArgs {
     double tol;
 };
 int multi_width(int nrhs);
+// launch(std::integral_constant<int, W>{}) for W = multi_width(nrhs): THE dispatch over the five kernel widths
+template <class Launch>
+auto for_multi_width(int nrhs, Launch &&launch)
+{
+    switch (multi_width(nrhs)) {
+    case 1: return launch(std::integral_constant<int, 1>{});
+    case 2: return launch(std::integral_constant<int, 2>{});
+    case 4: return launch(std::integral_constant<int, 4>{});
+    case 8: return launch(std::integral_constant<int, 8>{});
+    default: return launch(std::integral_constant<int, 16>{});
+    }
+}
 int multi_rows_per_wg(int width);
 int multi_gemv_grid(int n, int width);   // K1m workgroups = p.Ap partials per column
 int multi_update_grid(int n);            // K3m workgroups per column = r.r partials per column
@@ -527,16 +541,24 @@ hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const 
 struct MultiPcScalars {
     double rr[kMaxRhs][2];     // per column: r.r in rs's ping-pong (as Scalars::rr)
 };
-struct MultiPcArgs {
-    double *Z;                 // kMaxRhs x lda: z_j = M^-1 r_j (live columns only)
-    double *rzp;               // r.z partials, multi_update_grid(n) per column, beside MultiArgs::rrp
-    MultiPcScalars *mp;
+// The preconditioner M as the multi-column kernels take it (here and in cgx_lanczos_pc.hip); the host fills it with pc_factor
+// (cgx_precond.cpp).
+struct PcFactor {
     const double *dinv;        // point Jacobi: the inverse diagonal (lda doubles); nullptr = pivoted Cholesky:
     const double *L;           //   rank x lda, column-major at the matrix pitch
     int rank;
     const double *Cinv;        //   (delta I + L^T L)^-1 at pitch kLrLd
     const LrHead *head;        //   delta
     double *tpart;             //   kMaxRhs x lr_grid(n) x kLrLd: per column and 256-row tile the partials of t_j = L^T r_j
+};
+// Whether the K3m of this M can run on n rows: Jacobi always; the factor with a rank of 1 .. min(n, kLrMaxRank) and one workgroup
+// per 256-row tile, lr_grid(n) = multi_update_grid(n) <= kMaxVectorGrid of them.
+bool pc_factor_ok(int n, const PcFactor &f);
+struct MultiPcArgs {
+    double *Z;                 // kMaxRhs x lda: z_j = M^-1 r_j (live columns only)
+    double *rzp;               // r.z partials, multi_update_grid(n) per column, beside MultiArgs::rrp
+    MultiPcScalars *mp;
+    PcFactor M;
 };
 // K1m fused with the preconditioned head: g.r is Z, g.rrp the r.r partials; beta_j from r.z, the break from r.r.
 hipError_t launch_multi_gemv_pc(const MultiArgs &g, const MultiPcArgs &pc, hipStream_t s, hipEvent_t e0 = nullptr, hipEvent_t e1 = nullptr);
@@ -631,7 +653,7 @@ hipError_t launch_lanczos_close(int n, int nvec, int steps, const double *ww, La
 
 // ---- the same with a preconditioner (cgx_lanczos_pc, cgx_trace_slq_pc; cgx_lanczos_pc.hip) ----------------
 // Per column w (the side of M), u = M^-1 w and v_prev; K1m runs on the not yet normalised u.  LanczosScalars keeps its meaning with
-// z2 = eta0^2 = w_0 . M^-1 w_0.  dinv != nullptr: point Jacobi, one launch per step (grid tiles x nvec); else the pivoted-Cholesky
+// z2 = eta0^2 = w_0 . M^-1 w_0.  M.dinv != nullptr: point Jacobi, one launch per step (grid tiles x nvec); else the pivoted-Cholesky
 // factor, two launches of one workgroup per 256-row tile that serve every live column (the step, then the apply).
 struct LanczosPcArgs {
     int n, nvec;
@@ -647,12 +669,7 @@ struct LanczosPcArgs {
     LanczosScalars *ls;
     double *alpha, *beta;      // the histories: kMaxRhs rows of kMaxLanczosSteps
     int t;
-    const double *dinv;        // point Jacobi: the inverse diagonal (lda doubles); nullptr = pivoted Cholesky:
-    const double *L;           //   rank x lda, column-major at the matrix pitch
-    int rank;
-    const double *Cinv;        //   (delta I + L^T L)^-1 at pitch kLrLd
-    const LrHead *head;        //   delta
-    double *tpart;             //   kMaxRhs x lr_grid(n) x kLrLd: per column and tile the partials of t_j = L^T w_j
+    PcFactor M;                // tpart: the partials of t_j = L^T w_j
 };
 // The set-up from w = V0 as it is: u_0 = M^-1 w_0, v_-1 = 0, the w_0 . u_0 partials into wu_out, and per column eta0^2 folded in the
 // steps' order and the scalars reset; a column whose eta0^2 is 0, negative or not finite is marked bad and never runs.

@@ -53,16 +53,7 @@ cgx::LanczosPcArgs run_args(const cgx_ctx *ctx, const LanczosView &v, bool pc, i
     a.ls = v.ls;
     a.alpha = v.alpha;
     a.beta = v.beta;
-    if (pc && ctx->precond == CGX_PRECOND_JACOBI) {
-        a.dinv = ctx->shards[0].dinv;
-    } else if (pc) {
-        const cgx::LrWork w = lr_work(ctx);
-        a.L = ctx->lr_L;
-        a.rank = ctx->lr_L_rank;
-        a.Cinv = w.C;
-        a.head = w.head;
-        a.tpart = v.tpart;
-    }
+    if (pc) a.M = pc_factor(ctx, v.tpart);
     return a;
 }
 

@@ -16,8 +16,9 @@
 //   pivoted Cholesky   TWO launches of one workgroup per 256-row tile that serve every live column, shaped as cgx_multi_pc.hip's pair
 //                      so that the tile of L is read once per launch: the step (scalars and rows as above, and the tile's partials
 //                      of t_j = L^T w'_j) and the apply (t_j folded in ascending tile order, u_j = C^-1 t_j, u' = (w' - L u_j) /
-//                      delta, the w'.u' partial).  The chains are k_multi_lr_update's and k_multi_lr_apply's, restated: a frozen
-//                      Lanczos column is known by LanczosScalars::m, not by MultiScalars::done.
+//                      delta, the w'.u' partial).  The end of the step (lr_tile_partials) and the whole apply (lr_apply_cols) are
+//                      the ONE body of cgx_lowrank_cols.h that cgx_multi_pc.hip's pair runs; here are the step's head and rows,
+//                      and what makes a column live: LanczosScalars::m, not MultiScalars::done.
 // The host swaps w and v_prev between steps.  The set-up is the same launches in their INIT form (w taken as it is, v_prev = 0)
 // plus k_lpc_begin, which folds eta0^2 as every later step folds its partials and resets the column's scalars.
 //
@@ -27,7 +28,7 @@
 // same launch writes with a different meaning.  A frozen column has nothing written any more.  No floating-point atomics; no sum
 // depends on the column's position in the block; every offset is 64-bit.
 #include "cgx_kernels.h"
-#include "cgx_device.h"
+#include "cgx_lowrank_cols.h"
 
 namespace cgx {
 
@@ -35,12 +36,6 @@ namespace {
 
 constexpr double kLanczosBreak = 0x1.0p-36;   // beta_t <= 2^-36 max |alpha|: an invariant subspace (DESIGN.md sections 17, 18)
 constexpr double kDblMax = 1.7976931348623157e308;
-
-// the four waves' totals in block_sum<4>'s order
-__device__ __forceinline__ double fold4(const double (*red)[kMaxRhs], int j)
-{
-    return ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
-}
 
 // What step t decides for a column from ww = w_t . u_t, wAw = u_t . A u_t and the running max |alpha|; the writer stores it.
 struct StepHead {
@@ -132,13 +127,9 @@ __global__ __launch_bounds__(256) void k_lpc_jac_step(int n, long lda, double *_
     if (threadIdx.x == 0) wu_out[(long)j * g3 + blockIdx.x] = nw;
 }
 
-constexpr int kPcGroups = 4;                               // groups of 256 threads per workgroup, as cgx_multi_pc.hip
-constexpr int kPcThreads = 256 * kPcGroups;
-
 // Pivoted Cholesky, the step launch: workgroup b = rows [256 b, 256 b + 256) of EVERY live column, 1024 threads.  Thread group q
 // (256 threads, one per row) takes the columns j = q, q + 4, ...: the two folds, the column's decision, the rows.  Then, with the
-// tile of every w'_j in LDS, tpart[j][b][c] = sum over the tile of L[i][c] w'_j[i] in k_multi_lr_update's order (four rows per
-// lane ascending, one 8-row wave fold per group of eight columns of L; the 32 values of L a lane loads serve all columns).
+// tile of every w'_j in LDS, the tile's partials of t_j = L^T w'_j (lr_tile_partials).
 // s_live[j] afterwards: the column runs step t (INIT: every column < nvec).
 template <bool INIT>
 __global__ __launch_bounds__(kPcThreads) void k_lpc_lr_step(int n, long lda, int nvec, double *__restrict__ w,
@@ -214,140 +205,20 @@ __global__ __launch_bounds__(kPcThreads) void k_lpc_lr_step(int n, long lda, int
         }
     }
     __syncthreads();                                       // publishes rl
-    const int last = n - 1 - base;                         // >= 0: the grid has no workgroup past n
-    int ro[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ro[q] = (lane + 64 * q) <= last ? lane + 64 * q : last;   // clamped: w' is 0 there
-    for (int g = wv; 8 * g < rank; g += kPcThreads / 64) {
-        double lv[8][4];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int uc = 8 * g + c;
-            const double *col = L + (long)(uc < rank ? uc : rank - 1) * lda + base;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) lv[c][q] = col[ro[q]];
-        }
-        for (int j = 0; j < nvec; ++j) {
-            if (!s_live[j]) continue;                      // uniform
-            double rq[4], v[8];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rq[q] = rl[j][lane + 64 * q];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                double s = 0.0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s = fma(lv[c][q], rq[q], s);
-                v[c] = 8 * g + c < rank ? s : 0.0;
-            }
-            const int row = wave_sum_rows<8>(v, lane);
-            if ((lane & 7) == 0 && 8 * g + row < rank) tpart[((long)j * G + blockIdx.x) * kLrLd + 8 * g + row] = v[0];
-        }
-    }
+    lr_tile_partials(rl, s_live, nvec, L, lda, rank, n, base, tpart);
 }
 
-// acc[c] = sum_u col[u * stride] * vec[j0 + dj c][u] for CW columns at once: k_multi_lr_apply's chain -- one fma chain from +0.0
-// in ascending u, full trips of 16, the entries past count clamped to the last one and met by vec's zeros.
-template <int CW>
-__device__ __forceinline__ void lpc_chain_cols(const double *__restrict__ col, long stride, const double (*vec)[kLrMaxRank], int j0,
-                                               int dj, int count, double (&acc)[CW])
-{
-#pragma unroll
-    for (int c = 0; c < CW; ++c) acc[c] = 0.0;
-    for (int u = 0; u < count; u += 16) {
-        double w[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) w[q] = col[(long)(u + q < count ? u + q : count - 1) * stride];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-#pragma unroll
-            for (int c = 0; c < CW; ++c) acc[c] = fma(w[q], vec[j0 + dj * c][u + q], acc[c]);
-    }
-}
-
-// the apply launch's shape for a kernel width: NG thread groups of 256, each with CW = W / NG columns (j = q, q + NG, ...)
+// Pivoted Cholesky, the apply launch (lr_apply_cols): u'_j = M^-1 w'_j and the w'.u' partials of the columns that ran step t
+// (m > t); ls == nullptr: the set-up, every column < nvec.
 template <int W>
-struct LpcApplyShape {
-    static constexpr int NG = W < kPcGroups ? W : kPcGroups;
-    static constexpr int CW = W / NG;
-};
-
-// Pivoted Cholesky, the apply launch: workgroup b = the same tile of every live column; thread group q (one thread per row) takes
-// the columns j = q, q + NG, ...  t_j = the G tile partials in ascending order, u_j = C^-1 t_j in place of t_j, u' = (w' - L u_j)
-// / delta for the tile's rows, the w'.u' partial.  A column is live if it ran step t (m > t); ls == nullptr: the set-up, every
-// column < nvec.
-template <int W>
-__global__ __launch_bounds__(256 * LpcApplyShape<W>::NG) void k_lpc_lr_apply(int n, long lda, int nvec, const double *__restrict__ wn,
-                                                                             double *__restrict__ u, const double *__restrict__ L,
-                                                                             int rank, const double *__restrict__ Cinv,
-                                                                             const LrHead *head, const double *__restrict__ tpart,
-                                                                             const LanczosScalars *ls, int t,
-                                                                             double *__restrict__ wu_out)
+__global__ __launch_bounds__(256 * LrColsShape<W>::NG) void k_lpc_lr_apply(int n, long lda, int nvec, const double *__restrict__ wn,
+                                                                           double *__restrict__ u, const double *__restrict__ L,
+                                                                           int rank, const double *__restrict__ Cinv,
+                                                                           const LrHead *head, const double *__restrict__ tpart,
+                                                                           const LanczosScalars *ls, int t,
+                                                                           double *__restrict__ wu_out)
 {
-    constexpr int NG = LpcApplyShape<W>::NG, CW = LpcApplyShape<W>::CW;
-    __shared__ double tu[W][kLrMaxRank];
-    __shared__ double red[4][kMaxRhs];
-    __shared__ int s_live[W];
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const int lt = tid & 255, q = tid >> 8, wl = (tid >> 6) & 3;   // row of the tile, thread group, wave of the group
-    const int G = (int)gridDim.x;
-    if (tid < W) s_live[tid] = (tid < nvec && !(ls && ls->m[tid] <= t)) ? 1 : 0;
-    __syncthreads();
-    int any = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j) any |= s_live[j];
-    if (!any) return;                                      // every column is frozen (uniform)
-    const double delta = head->delta;
-    const int i = (int)blockIdx.x * 256 + lt;
-    const bool in = i < n;
-    const long ic = in ? i : n - 1;
-    double r_i[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        r_i[c] = wn[(long)(j < nvec ? j : nvec - 1) * lda + ic];
-    }
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        double s = 0.0;
-        if (s_live[j]) {                                   // uniform over the group
-            const double *tp = tpart + (long)j * G * kLrLd + (lt < rank ? lt : 0);
-            int g = 0;
-            for (; g + 16 <= G; g += 16) {
-                double a[16];
-#pragma unroll
-                for (int x = 0; x < 16; ++x) a[x] = tp[(long)(g + x) * kLrLd];
-#pragma unroll
-                for (int x = 0; x < 16; ++x) s += a[x];
-            }
-            for (; g < G; ++g) s += tp[(long)g * kLrLd];
-        }
-        tu[j][lt] = (lt < rank && s_live[j]) ? s : 0.0;    // zeros behind the rank: the chain's last trip
-    }
-    __syncthreads();
-    double acc[CW];
-    // C^-1 is symmetric bit for bit: row lt read as column lt, coalesced
-    lpc_chain_cols<CW>(Cinv + (lt < rank ? lt : 0), kLrLd, tu, q, NG, rank, acc);
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CW; ++c) tu[q + NG * c][lt] = lt < rank ? acc[c] : 0.0;
-    __syncthreads();
-    lpc_chain_cols<CW>(L + ic, lda, tu, q, NG, rank, acc);
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        double wu = 0.0;
-        if (s_live[j]) {                                   // uniform over the group
-            if (in) {
-                const double uv = (r_i[c] - acc[c]) / delta;
-                u[(long)j * lda + i] = uv;
-                wu = r_i[c] * uv;
-            }
-            wu = wave_sum(wu);
-            if (lane == 0) red[wl][j] = wu;
-        }
-    }
-    __syncthreads();
-    if (tid < W && s_live[tid]) wu_out[(long)tid * G + blockIdx.x] = fold4(red, tid);
+    lr_apply_cols<W>([ls, t](int j) { return !(ls && ls->m[j] <= t); }, n, lda, nvec, wn, u, L, rank, Cinv, head, tpart, wu_out);
 }
 
 // One workgroup per column: the last beta, and m = steps for a column that ran to the end.
@@ -394,31 +265,19 @@ __global__ __launch_bounds__(256) void k_lpc_probes(int n, long lda, int kind, u
     Z[(long)blockIdx.y * lda + i] = z;
 }
 
-template <int W>
-hipError_t launch_apply_width(const LanczosPcArgs &a, const double *wn, const LanczosScalars *frozen, double *wu_out, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_lpc_lr_apply<W>), dim3(lr_grid(a.n)), dim3(256 * LpcApplyShape<W>::NG), 0, s, a.n, a.lda, a.nvec, wn, a.u, a.L,
-                       a.rank, a.Cinv, a.head, a.tpart, frozen, a.t, wu_out);
-    return hipGetLastError();
-}
-
 hipError_t launch_apply(const LanczosPcArgs &a, const double *wn, const LanczosScalars *frozen, double *wu_out, hipStream_t s)
 {
-    switch (multi_width(a.nvec)) {
-    case 1: return launch_apply_width<1>(a, wn, frozen, wu_out, s);
-    case 2: return launch_apply_width<2>(a, wn, frozen, wu_out, s);
-    case 4: return launch_apply_width<4>(a, wn, frozen, wu_out, s);
-    case 8: return launch_apply_width<8>(a, wn, frozen, wu_out, s);
-    default: return launch_apply_width<16>(a, wn, frozen, wu_out, s);
-    }
+    return for_multi_width(a.nvec, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((k_lpc_lr_apply<W>), dim3(lr_grid(a.n)), dim3(256 * LrColsShape<W>::NG), 0, s, a.n, a.lda, a.nvec, wn, a.u, a.M.L,
+                           a.M.rank, a.M.Cinv, a.M.head, a.M.tpart, frozen, a.t, wu_out);
+        return hipGetLastError();
+    });
 }
 
 bool lpc_args_ok(const LanczosPcArgs &a)
 {
-    if (a.nvec < 1 || a.nvec > kMaxRhs || a.n < 1) return false;
-    if (a.dinv) return true;
-    const int g3 = multi_update_grid(a.n);
-    return a.rank >= 1 && a.rank <= kLrMaxRank && a.rank <= a.n && g3 == lr_grid(a.n) && g3 <= kMaxVectorGrid;
+    return a.nvec >= 1 && a.nvec <= kMaxRhs && a.n >= 1 && pc_factor_ok(a.n, a.M);
 }
 
 }  // namespace
@@ -427,12 +286,12 @@ hipError_t launch_lanczos_pc_init(const LanczosPcArgs &a, hipStream_t s)
 {
     if (!lpc_args_ok(a)) return hipErrorInvalidValue;
     const int g3 = multi_update_grid(a.n);
-    if (a.dinv) {
-        hipLaunchKernelGGL((k_lpc_jac_step<true>), dim3(g3, a.nvec), dim3(256), 0, s, a.n, a.lda, a.w, a.vprev, a.u, a.Y, a.dinv, a.k1p, a.g1,
+    if (a.M.dinv) {
+        hipLaunchKernelGGL((k_lpc_jac_step<true>), dim3(g3, a.nvec), dim3(256), 0, s, a.n, a.lda, a.w, a.vprev, a.u, a.Y, a.M.dinv, a.k1p, a.g1,
                            a.wu_in, a.wu_out, a.ls, a.alpha, a.beta, 0);
     } else {
         hipLaunchKernelGGL((k_lpc_lr_step<true>), dim3(g3), dim3(kPcThreads), 0, s, a.n, a.lda, a.nvec, a.w, a.vprev, a.Y, a.k1p, a.g1,
-                           a.wu_in, a.ls, a.alpha, a.beta, 0, a.L, a.rank, a.tpart);
+                           a.wu_in, a.ls, a.alpha, a.beta, 0, a.M.L, a.M.rank, a.M.tpart);
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
         e = launch_apply(a, a.w, nullptr, a.wu_out, s);
@@ -448,13 +307,13 @@ hipError_t launch_lanczos_pc_step(const LanczosPcArgs &a, hipStream_t s)
 {
     if (!lpc_args_ok(a) || a.t < 0 || a.t >= kMaxLanczosSteps) return hipErrorInvalidValue;
     const int g3 = multi_update_grid(a.n);
-    if (a.dinv) {
-        hipLaunchKernelGGL((k_lpc_jac_step<false>), dim3(g3, a.nvec), dim3(256), 0, s, a.n, a.lda, a.w, a.vprev, a.u, a.Y, a.dinv, a.k1p, a.g1,
+    if (a.M.dinv) {
+        hipLaunchKernelGGL((k_lpc_jac_step<false>), dim3(g3, a.nvec), dim3(256), 0, s, a.n, a.lda, a.w, a.vprev, a.u, a.Y, a.M.dinv, a.k1p, a.g1,
                            a.wu_in, a.wu_out, a.ls, a.alpha, a.beta, a.t);
         return hipGetLastError();
     }
     hipLaunchKernelGGL((k_lpc_lr_step<false>), dim3(g3), dim3(kPcThreads), 0, s, a.n, a.lda, a.nvec, a.w, a.vprev, a.Y, a.k1p, a.g1, a.wu_in,
-                       a.ls, a.alpha, a.beta, a.t, a.L, a.rank, a.tpart);
+                       a.ls, a.alpha, a.beta, a.t, a.M.L, a.M.rank, a.M.tpart);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     return launch_apply(a, a.vprev, a.ls, a.wu_out, s);    // w_(t+1) lies over v_(t-1)

@@ -11,7 +11,7 @@
 #include <climits>
 #include <cmath>
 
-#include "cgx_device.h"
+#include "cgx_lowrank_cols.h"
 
 namespace cgx {
 
@@ -313,20 +313,8 @@ __global__ __launch_bounds__(256) void k_lr_apply(int n, const double *__restric
     const int i = (int)blockIdx.x * 256 + tid;
     const bool in = i < n;
     const double r_i = in ? r[i] : 0.0;
-    {
-        const double *tp = tpart + (tid < rank ? tid : 0);
-        double s = 0.0;
-        int g = 0;
-        for (; g + 16 <= G; g += 16) {
-            double a[16];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) a[q] = tp[(long)(g + q) * kLrLd];
-#pragma unroll
-            for (int q = 0; q < 16; ++q) s += a[q];
-        }
-        for (; g < G; ++g) s += tp[(long)g * kLrLd];
-        ts[tid] = tid < rank ? s : 0.0;   // zeros behind the rank: lr_chain's last trip
-    }
+    const double t = lr_fold_tiles(tpart + (tid < rank ? tid : 0), G);
+    ts[tid] = tid < rank ? t : 0.0;   // zeros behind the rank: lr_chain's last trip
     __syncthreads();
     // C^-1 is symmetric bit for bit: row tid read as column tid, coalesced
     us[tid] = tid < rank ? lr_chain<16>(Cinv + tid, kLrLd, ts, rank) : 0.0;
@@ -344,6 +332,13 @@ __global__ __launch_bounds__(256) void k_lr_apply(int n, const double *__restric
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------
 int lr_grid(int n) { return (n + 255) / 256; }
+
+bool pc_factor_ok(int n, const PcFactor &f)
+{
+    if (f.dinv) return true;
+    const int g3 = multi_update_grid(n);
+    return f.rank >= 1 && f.rank <= kLrMaxRank && f.rank <= n && g3 == lr_grid(n) && g3 <= kMaxVectorGrid;
+}
 
 hipError_t launch_lr_init(const double *A, long lda, int n, const LrWork &w, hipStream_t s)
 {

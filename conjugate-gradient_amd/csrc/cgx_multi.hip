@@ -167,13 +167,7 @@ int multi_update_grid(int n) { return (n + 255) / 256; }
 hipError_t launch_multi_gemv(const MultiArgs &g, bool fused, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (g.nrhs < 1 || g.nrhs > kMaxRhs || g.n < 1) return hipErrorInvalidValue;
-    switch (multi_width(g.nrhs)) {
-    case 1: return launch_width<1>(g, fused, s, e0, e1);
-    case 2: return launch_width<2>(g, fused, s, e0, e1);
-    case 4: return launch_width<4>(g, fused, s, e0, e1);
-    case 8: return launch_width<8>(g, fused, s, e0, e1);
-    default: return launch_width<16>(g, fused, s, e0, e1);
-    }
+    return for_multi_width(g.nrhs, [&](auto w) { return launch_width<decltype(w)::value>(g, fused, s, e0, e1); });
 }
 
 hipError_t launch_multi_update(int n, long lda, int nrhs, const double *p, const double *Y, const double *partials, int g1, double *x,

@@ -95,16 +95,7 @@ cgx::MultiPcArgs pc_args(const cgx_ctx *ctx, const PcView &pv)
     a.Z = pv.Z;
     a.rzp = pv.rzp;
     a.mp = pv.mp;
-    if (ctx->precond == CGX_PRECOND_JACOBI) {
-        a.dinv = ctx->shards[0].dinv;
-    } else {
-        const cgx::LrWork w = lr_work(ctx);
-        a.L = ctx->lr_L;
-        a.rank = ctx->lr_L_rank;
-        a.Cinv = w.C;
-        a.head = w.head;
-        a.tpart = pv.tpart;
-    }
+    a.M = pc_factor(ctx, pv.tpart);
     return a;
 }
 

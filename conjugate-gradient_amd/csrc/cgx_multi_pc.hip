@@ -12,12 +12,14 @@
 //               apply    t_j folded over the tiles in ascending order, u_j = C^-1 t_j, z_j = (r_j - L u_j) / delta, r.z partial;
 //                        C^-1's and L's entries are loaded once per 16-column trip and used for all W columns
 //               Per (row, column) the chains are k_lr_update's and k_lr_apply's (cgx_lowrank.hip): z_j for a given r_j has the bits
-//               the single path gives it.
+//               the single path gives it.  The end of the update (lr_tile_partials) and the whole apply (lr_apply_cols) are ONE
+//               body in cgx_lowrank_cols.h, which cgx_lanczos_pc.hip's pair runs too; here are the update's head -- alpha_j and
+//               the rows of CG -- and what makes a column live: MultiScalars::done.
 //
 // A frozen column has nothing written (x, r, z, p, scalars, partials); columns nrhs .. W-1 are masked by nrhs.  No floating-point
 // atomics; every sum has a fixed order that does not depend on the column's position among the others.
 #include "cgx_kernels.h"
-#include "cgx_device.h"
+#include "cgx_lowrank_cols.h"
 
 #include <hip/hip_ext.h>
 
@@ -47,12 +49,6 @@ __global__ __launch_bounds__(kMultiThreads) void k_multi_close_pc(MultiScalars *
         double beta;
         (void)multi_head<true>(ms, mp, rzp, rrp, g3, j, k, tol, true, &beta);
     }
-}
-
-// the four waves' totals in block_sum<4>'s order
-__device__ __forceinline__ double fold4(const double (*red)[kMaxRhs], int j)
-{
-    return ((red[0][j] + red[1][j]) + red[2][j]) + red[3][j];
 }
 
 // K3m, Jacobi: workgroup (b, j) = rows [256 b, 256 b + 256) of column j, as k_multi_update; rho_j = ms->rs[j][parity].
@@ -97,15 +93,10 @@ __global__ __launch_bounds__(256) void k_multi_update_jac(int n, long lda, const
     }
 }
 
-constexpr int kPcGroups = 4;                               // groups of 256 threads per workgroup of the update launch
-constexpr int kPcThreads = 256 * kPcGroups;
-
 // K3m, pivoted Cholesky, the update launch: workgroup b = rows [256 b, 256 b + 256) of EVERY live column, 1024 threads.  Thread
 // group q (256 threads, one per row) takes the columns j = q, q + 4, ...: p.Ap from K1m's g1 partials in K3's order, alpha_j,
 // x_j += alpha_j p_j, r_j -= alpha_j Y_j, the r.r partial (per column the sums of k_multi_update: a wave's 64 rows, then the
-// group's four waves in order).  Then, with the tile of every r_j in LDS, tpart[j][b][u] = sum over the tile of L[i][u] r_j[i] --
-// k_lr_update's sums (four rows per lane in ascending order, one 8-row wave fold per group of eight columns of L): the groups
-// of eight columns go over the 16 waves, and the 32 values of L a lane loads serve all columns.
+// group's four waves in order).  Then, with the tile of every r_j in LDS, the tile's partials of t_j = L^T r_j (lr_tile_partials).
 template <bool INIT>
 __global__ __launch_bounds__(kPcThreads) void k_multi_lr_update(int n, long lda, int nrhs, const double *__restrict__ p,
                                                                 const double *__restrict__ Y, const double *__restrict__ partials,
@@ -171,139 +162,19 @@ __global__ __launch_bounds__(kPcThreads) void k_multi_lr_update(int n, long lda,
     }
     __syncthreads();                                       // publishes rl and red2
     if (tid < nrhs && s_live[tid]) rrp[(long)tid * gridDim.x + blockIdx.x] = fold4(red2, tid);
-    const int last = n - 1 - base;                         // >= 0: the grid has no workgroup past n
-    int ro[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) ro[q] = (lane + 64 * q) <= last ? lane + 64 * q : last;   // clamped: r is 0 there
-    for (int g = w; 8 * g < rank; g += kPcThreads / 64) {
-        double lv[8][4];
-#pragma unroll
-        for (int c = 0; c < 8; ++c) {
-            const int u = 8 * g + c;
-            const double *col = L + (long)(u < rank ? u : rank - 1) * lda + base;
-#pragma unroll
-            for (int q = 0; q < 4; ++q) lv[c][q] = col[ro[q]];
-        }
-        for (int j = 0; j < nrhs; ++j) {
-            if (!s_live[j]) continue;                      // uniform
-            double rq[4], v[8];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) rq[q] = rl[j][lane + 64 * q];
-#pragma unroll
-            for (int c = 0; c < 8; ++c) {
-                double s = 0.0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) s = fma(lv[c][q], rq[q], s);
-                v[c] = 8 * g + c < rank ? s : 0.0;
-            }
-            const int row = wave_sum_rows<8>(v, lane);
-            if ((lane & 7) == 0 && 8 * g + row < rank) tpart[((long)j * gridDim.x + blockIdx.x) * kLrLd + 8 * g + row] = v[0];
-        }
-    }
+    lr_tile_partials(rl, s_live, nrhs, L, lda, rank, n, base, tpart);
 }
 
-// acc[c] = sum_u col[u * stride] * vec[j0 + dj c][u] for CW columns at once: per column lr_chain<16>'s chain (cgx_lowrank.hip) --
-// one fma chain from +0.0 in ascending u, full trips of 16, the columns past count clamped to the last one and met by vec's
-// zeros -- with every trip's 16 values loaded once for all of them.
-template <int CW>
-__device__ __forceinline__ void lr_chain_cols(const double *__restrict__ col, long stride, const double (*vec)[kLrMaxRank], int j0,
-                                              int dj, int count, double (&acc)[CW])
-{
-#pragma unroll
-    for (int c = 0; c < CW; ++c) acc[c] = 0.0;
-    for (int u = 0; u < count; u += 16) {
-        double w[16];
-#pragma unroll
-        for (int q = 0; q < 16; ++q) w[q] = col[(long)(u + q < count ? u + q : count - 1) * stride];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-#pragma unroll
-            for (int c = 0; c < CW; ++c) acc[c] = fma(w[q], vec[j0 + dj * c][u + q], acc[c]);
-    }
-}
-
-// the apply launch's shape for a kernel width: NG thread groups of 256, each with CW = W / NG columns (j = q, q + NG, ...)
+// K3m, pivoted Cholesky, the apply launch (lr_apply_cols): z_j = M^-1 r_j and the r.z partials of the columns that have not taken
+// the break.  ms == nullptr: no frozen columns (set-up, probe).
 template <int W>
-struct ApplyShape {
-    static constexpr int NG = W < kPcGroups ? W : kPcGroups;
-    static constexpr int CW = W / NG;
-};
-
-// K3m, pivoted Cholesky, the apply launch: workgroup b = the same tile of every live column; thread group q (one thread per row)
-// takes the columns j = q, q + NG, ...  t_j = the G tile partials in ascending order (k_lr_apply's fold), u_j = C^-1 t_j in place
-// of t_j, z_j = (r_j - L u_j) / delta for the tile's rows, the r.z partial.  ms == nullptr: no frozen columns (set-up, probe).
-template <int W>
-__global__ __launch_bounds__(256 * ApplyShape<W>::NG) void k_multi_lr_apply(int n, long lda, int nrhs, const double *__restrict__ r,
-                                                                            double *__restrict__ z, const double *__restrict__ L,
-                                                                            int rank, const double *__restrict__ Cinv,
-                                                                            const LrHead *head, const double *__restrict__ tpart,
-                                                                            const MultiScalars *ms, double *__restrict__ rzp)
+__global__ __launch_bounds__(256 * LrColsShape<W>::NG) void k_multi_lr_apply(int n, long lda, int nrhs, const double *__restrict__ r,
+                                                                             double *__restrict__ z, const double *__restrict__ L,
+                                                                             int rank, const double *__restrict__ Cinv,
+                                                                             const LrHead *head, const double *__restrict__ tpart,
+                                                                             const MultiScalars *ms, double *__restrict__ rzp)
 {
-    constexpr int NG = ApplyShape<W>::NG, CW = ApplyShape<W>::CW;
-    __shared__ double tu[W][kLrMaxRank];
-    __shared__ double red[4][kMaxRhs];
-    __shared__ int s_live[W];
-    const int tid = (int)threadIdx.x, lane = tid & 63;
-    const int lt = tid & 255, q = tid >> 8, wl = (tid >> 6) & 3;   // row of the tile, thread group, wave of the group
-    const int G = (int)gridDim.x;
-    if (tid < W) s_live[tid] = (tid < nrhs && !(ms && ms->done[tid])) ? 1 : 0;
-    __syncthreads();
-    int any = 0;
-#pragma unroll
-    for (int j = 0; j < W; ++j) any |= s_live[j];
-    if (!any) return;                                      // every column is frozen (uniform)
-    const double delta = head->delta;
-    const int i = (int)blockIdx.x * 256 + lt;
-    const bool in = i < n;
-    const long ic = in ? i : n - 1;
-    double r_i[CW];
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        r_i[c] = r[(long)(j < nrhs ? j : nrhs - 1) * lda + ic];
-    }
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        double s = 0.0;
-        if (s_live[j]) {                                   // uniform over the group
-            const double *tp = tpart + (long)j * G * kLrLd + (lt < rank ? lt : 0);
-            int g = 0;
-            for (; g + 16 <= G; g += 16) {
-                double a[16];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) a[t] = tp[(long)(g + t) * kLrLd];
-#pragma unroll
-                for (int t = 0; t < 16; ++t) s += a[t];
-            }
-            for (; g < G; ++g) s += tp[(long)g * kLrLd];
-        }
-        tu[j][lt] = (lt < rank && s_live[j]) ? s : 0.0;    // zeros behind the rank: the chain's last trip
-    }
-    __syncthreads();
-    double acc[CW];
-    // C^-1 is symmetric bit for bit: row lt read as column lt, coalesced
-    lr_chain_cols<CW>(Cinv + (lt < rank ? lt : 0), kLrLd, tu, q, NG, rank, acc);
-    __syncthreads();
-#pragma unroll
-    for (int c = 0; c < CW; ++c) tu[q + NG * c][lt] = lt < rank ? acc[c] : 0.0;
-    __syncthreads();
-    lr_chain_cols<CW>(L + ic, lda, tu, q, NG, rank, acc);
-#pragma unroll
-    for (int c = 0; c < CW; ++c) {
-        const int j = q + NG * c;
-        double rz = 0.0;
-        if (s_live[j]) {                                   // uniform over the group
-            if (in) {
-                const double zv = (r_i[c] - acc[c]) / delta;
-                z[(long)j * lda + i] = zv;
-                rz = r_i[c] * zv;
-            }
-            rz = wave_sum(rz);
-            if (lane == 0) red[wl][j] = rz;
-        }
-    }
-    __syncthreads();
-    if (tid < W && s_live[tid]) rzp[(long)tid * G + blockIdx.x] = fold4(red, tid);
+    lr_apply_cols<W>([ms](int j) { return !(ms && ms->done[j]); }, n, lda, nrhs, r, z, L, rank, Cinv, head, tpart, rzp);
 }
 
 template <int W>
@@ -314,59 +185,44 @@ hipError_t launch_gemv_width(const MultiArgs &g, const MultiPcArgs &pc, hipStrea
     return hipGetLastError();
 }
 
-template <int W>
-hipError_t launch_apply_width(int n, long lda, int nrhs, const double *r, const MultiPcArgs &pc, const MultiScalars *ms, hipStream_t s)
-{
-    hipLaunchKernelGGL((k_multi_lr_apply<W>), dim3(lr_grid(n)), dim3(256 * ApplyShape<W>::NG), 0, s, n, lda, nrhs, r, pc.Z, pc.L, pc.rank, pc.Cinv, pc.head,
-                       pc.tpart, ms, pc.rzp);
-    return hipGetLastError();
-}
-
 }  // namespace
 
 hipError_t launch_multi_gemv_pc(const MultiArgs &g, const MultiPcArgs &pc, hipStream_t s, hipEvent_t e0, hipEvent_t e1)
 {
     if (g.nrhs < 1 || g.nrhs > kMaxRhs || g.n < 1) return hipErrorInvalidValue;
-    switch (multi_width(g.nrhs)) {
-    case 1: return launch_gemv_width<1>(g, pc, s, e0, e1);
-    case 2: return launch_gemv_width<2>(g, pc, s, e0, e1);
-    case 4: return launch_gemv_width<4>(g, pc, s, e0, e1);
-    case 8: return launch_gemv_width<8>(g, pc, s, e0, e1);
-    default: return launch_gemv_width<16>(g, pc, s, e0, e1);
-    }
+    return for_multi_width(g.nrhs, [&](auto w) { return launch_gemv_width<decltype(w)::value>(g, pc, s, e0, e1); });
 }
 
 hipError_t launch_multi_update_pc(int n, long lda, int nrhs, const double *p, const double *Y, const double *partials, int g1, double *x,
                                   double *r, double *rrp, MultiScalars *ms, int parity, const MultiPcArgs &pc, bool init, hipStream_t s)
 {
-    if (nrhs < 1 || nrhs > kMaxRhs || n < 1) return hipErrorInvalidValue;
+    if (nrhs < 1 || nrhs > kMaxRhs || n < 1 || !pc_factor_ok(n, pc.M)) return hipErrorInvalidValue;
+    const PcFactor &M = pc.M;
     const int g3 = multi_update_grid(n);
-    if (pc.dinv) {
+    if (M.dinv) {
         if (init)
-            hipLaunchKernelGGL((k_multi_update_jac<true>), dim3(g3, nrhs), dim3(256), 0, s, n, lda, p, Y, partials, g1, x, r, pc.Z, pc.dinv,
+            hipLaunchKernelGGL((k_multi_update_jac<true>), dim3(g3, nrhs), dim3(256), 0, s, n, lda, p, Y, partials, g1, x, r, pc.Z, M.dinv,
                                pc.rzp, rrp, ms, parity);
         else
-            hipLaunchKernelGGL((k_multi_update_jac<false>), dim3(g3, nrhs), dim3(256), 0, s, n, lda, p, Y, partials, g1, x, r, pc.Z, pc.dinv,
+            hipLaunchKernelGGL((k_multi_update_jac<false>), dim3(g3, nrhs), dim3(256), 0, s, n, lda, p, Y, partials, g1, x, r, pc.Z, M.dinv,
                                pc.rzp, rrp, ms, parity);
         return hipGetLastError();
     }
-    if (pc.rank < 1 || pc.rank > kLrMaxRank || g3 != lr_grid(n) || g3 > kMaxVectorGrid) return hipErrorInvalidValue;
     if (init)
         hipLaunchKernelGGL((k_multi_lr_update<true>), dim3(g3), dim3(kPcThreads), 0, s, n, lda, nrhs, p, Y, partials, g1, x, r, rrp, ms, parity,
-                           pc.L, pc.rank, pc.tpart);
+                           M.L, M.rank, M.tpart);
     else
         hipLaunchKernelGGL((k_multi_lr_update<false>), dim3(g3), dim3(kPcThreads), 0, s, n, lda, nrhs, p, Y, partials, g1, x, r, rrp, ms, parity,
-                           pc.L, pc.rank, pc.tpart);
+                           M.L, M.rank, M.tpart);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     const MultiScalars *frozen = init ? nullptr : ms;
-    switch (multi_width(nrhs)) {
-    case 1: return launch_apply_width<1>(n, lda, nrhs, r, pc, frozen, s);
-    case 2: return launch_apply_width<2>(n, lda, nrhs, r, pc, frozen, s);
-    case 4: return launch_apply_width<4>(n, lda, nrhs, r, pc, frozen, s);
-    case 8: return launch_apply_width<8>(n, lda, nrhs, r, pc, frozen, s);
-    default: return launch_apply_width<16>(n, lda, nrhs, r, pc, frozen, s);
-    }
+    return for_multi_width(nrhs, [&](auto w) {
+        constexpr int W = decltype(w)::value;
+        hipLaunchKernelGGL((k_multi_lr_apply<W>), dim3(g3), dim3(256 * LrColsShape<W>::NG), 0, s, n, lda, nrhs, r, pc.Z, M.L, M.rank, M.Cinv,
+                           M.head, M.tpart, frozen, pc.rzp);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_multi_close_pc(MultiScalars *ms, const MultiPcArgs &pc, const double *rrp, int n, int nrhs, int k, double tol,

@@ -180,6 +180,22 @@ cgx::LrWork lr_work(const cgx_ctx *ctx)
     return w;
 }
 
+cgx::PcFactor pc_factor(const cgx_ctx *ctx, double *tpart)
+{
+    cgx::PcFactor f{};
+    if (ctx->precond == CGX_PRECOND_JACOBI) {
+        f.dinv = ctx->shards[0].dinv;
+    } else {
+        const cgx::LrWork w = lr_work(ctx);
+        f.L = ctx->lr_L;
+        f.rank = ctx->lr_L_rank;
+        f.Cinv = w.C;
+        f.head = w.head;
+        f.tpart = tpart;
+    }
+    return f;
+}
+
 // One GPU, inside cgx_solve_begin: the refusals, the buffers, and -- once per matrix, rank and shift -- the factor: rank launches
 // of the step kernel, delta, C = delta I + L^T L and its inverse (block Jacobi's sweep on one block), all in stream order; the
 // head (failed step / row, delta) and the inversion's word are read back once behind the last of them.

@@ -255,13 +255,7 @@ hipError_t launch_shift_update(const ShiftArgs &a, hipStream_t s)
 {
     if (a.nshift < 1 || a.nshift > kMaxShifts || a.n < 1 || a.lda < a.n || a.nrr < 1 || a.npap < 1) return hipErrorInvalidValue;
     const dim3 grid(update_xr_grid(a.n)), block(256);
-    switch (multi_width(a.nshift)) {
-    case 1: hipLaunchKernelGGL(k_shift_update<1>, grid, block, 0, s, a); break;
-    case 2: hipLaunchKernelGGL(k_shift_update<2>, grid, block, 0, s, a); break;
-    case 4: hipLaunchKernelGGL(k_shift_update<4>, grid, block, 0, s, a); break;
-    case 8: hipLaunchKernelGGL(k_shift_update<8>, grid, block, 0, s, a); break;
-    default: hipLaunchKernelGGL(k_shift_update<16>, grid, block, 0, s, a); break;
-    }
+    for_multi_width(a.nshift, [&](auto w) { hipLaunchKernelGGL(k_shift_update<decltype(w)::value>, grid, block, 0, s, a); });
     return hipGetLastError();
 }
 

@@ -2,9 +2,10 @@
 every kernel width.
 
 The other modules stop at n = 1101, G = ceil(n / 256) = 5 tiles, and at the widths 1, 3, 8, 16.  The fold of t = L^T r over the tiles
-runs 16 tiles at a time with a scalar tail (k_lr_apply, k_multi_lr_apply, k_lpc_lr_apply), the apply kernels are templates of the
-width 1, 2, 4, 8 or 16 with dead columns in a partly filled one, and a Lanczos column that freezes under this preconditioner goes
-through k_lpc_lr_step / k_lpc_lr_apply, not through the Jacobi kernel the breakdown test runs.  Here:
+runs 16 tiles at a time with a scalar tail (lr_fold_tiles in csrc/cgx_lowrank_cols.h: one function, called by k_lr_apply and by the
+one apply body lr_apply_cols that k_multi_lr_apply and k_lpc_lr_apply wrap), the apply kernels are templates of the width 1, 2, 4,
+8 or 16 with dead columns in a partly filled one, and a Lanczos column that freezes under this preconditioner goes through
+k_lpc_lr_step / k_lpc_lr_apply, not through the Jacobi kernel the breakdown test runs.  Here:
 
   n = 4096   G = 16   one full trip of the fold, no tail, no ragged tile
   n = 4100   G = 17   one trip and a tail of one tile, whose last tile has 4 rows
