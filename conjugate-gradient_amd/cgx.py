@@ -33,7 +33,7 @@ EXPORTS = [
     "cgx_probe_get_source_term", "cgx_probe_set_fault_after", "cgx_probe_set_resident_limit", "cgx_probe_persistent_plan",
     "cgx_probe_parse_matrix_market", "cgx_probe_p2p_mailbox_to_host", "cgx_probe_fill_matrix_hash",
     "cgx_probe_set_p2p_epoch", "cgx_probe_get_p2p_epoch", "cgx_probe_p2p_host_mailboxes", "cgx_probe_resident_test",
-    "cgx_solve_multi", "cgx_probe_gemv_multi", "cgx_solve_shifted",
+    "cgx_solve_multi", "cgx_probe_gemv_multi", "cgx_solve_shifted", "cgx_solve_minres",
     "cgx_set_preconditioner", "cgx_get_preconditioner",
     "cgx_set_preconditioner_block", "cgx_get_preconditioner_block", "cgx_probe_get_precond_blocks",
     "cgx_set_matrix_csr", "cgx_get_matrix_nnz",
@@ -55,6 +55,7 @@ MAX_EIGENPAIRS = 16                # CGX_MAX_EIGENPAIRS
 EIGS_SLOT_CHUNK = 32               # kEigsChunk (csrc/cgx_kernels.h): basis slots per workgroup of the projection kernel
 _EIG_NAMES = {"largest": EIG_LARGEST, "smallest": EIG_SMALLEST}
 MAX_SHIFTS = 16   # CGX_MAX_SHIFTS: shifts of one cgx_solve_shifted call
+MAX_MINRES_SHIFTS = 16   # CGX_MAX_MINRES_SHIFTS: shifts of one cgx_solve_minres call
 PRECOND_NONE, PRECOND_JACOBI = 0, 1   # CGX_PRECOND_*: cgx_set_preconditioner
 PRECOND_PIVCHOL = 2                   # the pivoted-Cholesky low-rank factor: one GPU, dense storage
 MAX_PRECOND_RANK = 256                # CGX_MAX_PRECOND_RANK: cgx_set_preconditioner_rank
@@ -173,6 +174,7 @@ def lib():
         L.cgx_solve_multi_pc.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long, C.POINTER(Result)]
         L.cgx_probe_multi_pc_apply.argtypes = [vp, C.c_int, dp, C.c_long, dp, C.c_long]
         L.cgx_solve_shifted.argtypes = [vp, C.c_int, dp, dp, C.c_long, C.POINTER(Result)]
+        L.cgx_solve_minres.argtypes = [vp, C.c_int, dp, dp, C.c_long, C.POINTER(Result)]
         L.cgx_lanczos.argtypes = [vp, C.c_int, C.c_int, dp, C.c_long, dp, dp, ip]
         L.cgx_trace_slq.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.c_ulonglong, dp, C.c_long, dp, dp, dp, dp]
         L.cgx_tridiag_quadrature.argtypes = [C.c_int, dp, dp, dp, dp]
@@ -565,6 +567,18 @@ class CGSolver:
         X = np.zeros((k, n), dtype=np.float64)
         res = (Result * max(k, 1))()
         self._check(lib().cgx_solve_shifted(self._h, int(k), _dp(sig), _dp(X), int(n), res))
+        return X, [res[j].as_dict() for j in range(k)]
+
+    def solve_minres(self, shifts):
+        """shifts: finite sigma_j of either sign (at most MAX_MINRES_SHIFTS).  Returns (X, [result dicts]), X of shape
+        (len(shifts), n): row j solves (A + sigma_j I) x = b for the current matrix, taken as symmetric (it need not be definite),
+        and source term from a zero guess, all shifts on one Lanczos recurrence with one pass over A per iteration (MINRES,
+        cgx_solve_minres)."""
+        sig = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
+        k, n = sig.size, self.n()
+        X = np.zeros((k, n), dtype=np.float64)
+        res = (Result * max(k, 1))()
+        self._check(lib().cgx_solve_minres(self._h, int(k), _dp(sig), _dp(X), int(n), res))
         return X, [res[j].as_dict() for j in range(k)]
 
     def lanczos(self, V0, steps):

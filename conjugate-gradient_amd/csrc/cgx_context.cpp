@@ -116,6 +116,9 @@ void free_problem(cgx_ctx *ctx)
     (void)hipFree(ctx->shift);
     ctx->shift = nullptr;
     ctx->shift_bytes = 0;
+    (void)hipFree(ctx->minres);
+    ctx->minres = nullptr;
+    ctx->minres_bytes = 0;
     (void)hipFree(ctx->lanczos);
     ctx->lanczos = nullptr;
     ctx->lanczos_bytes = 0;

@@ -193,6 +193,11 @@ struct cgx_ctx {
     // block of the final verification and the shift scalars; made on first use, freed with the problem
     double *shift = nullptr;
     size_t shift_bytes = 0;
+    // MINRES (cgx_solve_minres, cgx_minres_host.cpp): ONE device block holding the kMaxMinresShifts-wide x and the two direction
+    // blocks of the shifts, the block of the final verification, the two recurrence vectors, the partials and the scalars; made on
+    // first use, freed with the problem
+    double *minres = nullptr;
+    size_t minres_bytes = 0;
     // Lanczos quadrature (cgx_lanczos, cgx_trace_slq, cgx_lanczos_host.cpp): ONE device block holding the two kMaxRhs-wide vector
     // blocks of the recurrence, Y, the partials, the alpha / beta histories and the scalars; made on first use, freed with the problem
     double *lanczos = nullptr;
@@ -364,6 +369,13 @@ double one_gpu_gemv_bytes(const cgx_ctx *ctx);             // algorithmic bytes 
 cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn);
 // A side block of the context (cgx_ctx::multi, cgx_ctx::shift): allocated and zeroed on first use, freed again if that fails.
 cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes);
+
+// cgx_shift_host.cpp: the true residuals of nshift shifted systems (cgx_solve_shifted, cgx_solve_minres), enqueued on the context's
+// stream.  X, Y: kMaxShifts x lda blocks (shift j at + j * lda); Y_j = A x_j -- dense: one multi-vector pass at full width with
+// k1p / ms as its partials and scalar block, CSR: one SpMV per shift -- then ss->norms[j] = ||Y_j + ss->sigma[j] x_j - b||^2,
+// ||b||^2, ||x_j||^2.
+cgx_status shifted_residual_norms(cgx_ctx *ctx, int nshift, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
+                                  cgx::ShiftScalars *ss);
 
 // ... and one that grows (cgx_ctx::funm, cgx_ctx::eigs): made on first use, made again when a call needs more than it holds.
 // detail: what the out-of-memory message says the bytes are for.

@@ -617,6 +617,51 @@ hipError_t launch_shift_close(ShiftScalars *ss, const double *rrp, int nrr, int 
 hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, const double *b, const double *X, ShiftScalars *ss,
                               hipStream_t s);
 
+// ---- MINRES: (A + sigma_j I) x_j = b for up to kMaxMinresShifts shifts of either sign, A symmetric (cgx_minres.hip) -----------
+// One Lanczos recurrence from r0 = b serves every shift.  Launch t is the plain K1 of the shard's plan on
+// the not yet normalised w_t, then launch_minres_step, which finishes Lanczos step t and closes column t - 1 of every shift.
+// X and D[2] (the x of the shifts and their last two search directions) are column-major at pitch lda like the shift block.
+constexpr int kMaxMinresShifts = 16;           // = CGX_MAX_MINRES_SHIFTS
+constexpr int kMinresLive = 0x7fffffff;        // frozen_at / end_at of a shift / a loop that is still running
+struct MinresScalars {
+    int    done;                   // the two words the host polls: raised with end_at
+    int    end_at;                 // the launch that ended the loop (every shift frozen, or a breakdown); later launches exit at once
+    int    pad[2];
+    double alpha[2];               // alpha_t at [t & 1]: launch t reads alpha_(t-1) and writes alpha_t, never the slot another
+    double amax[2];                // workgroup of the same launch reads; max over s <= t of |alpha_s| likewise
+    double sigma[kMaxMinresShifts];
+    // the rotation state of shift j in front of column k at [(k + 1) & 1][j]: launch t = k + 1 reads it and writes column k + 1's
+    double cs[2][kMaxMinresShifts], sn[2][kMaxMinresShifts], dbar[2][kMaxMinresShifts], eps[2][kMaxMinresShifts];
+    double phibar[2][kMaxMinresShifts];
+    double res_last[kMaxMinresShifts];   // |phibar_(k+1)| behind the shift's last column k
+    double res_prev[kMaxMinresShifts];   // |phibar_k|
+    int    frozen_at[kMaxMinresShifts];  // the column that froze the shift (kMinresLive: running); a number, not a flag, as
+                                         // ShiftScalars::frozen_at
+    int    conv[kMaxMinresShifts];       // 1 = frozen below tol, or by a breakdown that left the shift regular
+};
+struct MinresArgs {
+    int n, nshift;
+    long lda;
+    double *w, *vprev;             // launch t: w_t (becomes v_t) and v_(t-1) (becomes w_(t+1)); the host swaps them between launches
+    const double *Y;               // K1's product A w_t
+    const double *k1p;             // ... and its w_t . A w_t partials
+    int nk1p;
+    const double *ww_in;           // the ||w_t||^2 partials of launch t - 1 (t = 0: of the init kernel), update_xr_grid(n) of them
+    double *ww_out;
+    double *X, *D[2];              // d_m of shift j at D[m & 1] + j * lda
+    MinresScalars *ms;
+    int t;                         // the close kernel: the launches that were enqueued
+    double tol;
+};
+// w_0 = b and v_-1 = 0 (zero padded up to lda), x_j = d_j = 0 for j < nshift, the ||b||^2 partials, the scalar block, and sigma /
+// zeroed norms in the block launch_shift_norms takes behind the loop (sigma: host array).
+hipError_t launch_minres_init(const MinresArgs &a, const double *sigma, const double *b, ShiftScalars *vs, hipStream_t s);
+// Behind K1 of launch t: beta_t, alpha_t, the breakdown test, column t - 1 of every running shift (x update, freeze, loop end),
+// v_t, w_(t+1) and its ||.||^2 partials.
+hipError_t launch_minres_step(const MinresArgs &a, hipStream_t s);
+// Behind the last launch (a.t launches were enqueued): the last column with beta from the last partials, unless the loop has ended.
+hipError_t launch_minres_close(const MinresArgs &a, hipStream_t s);
+
 // ---- multi-vector Lanczos for Gauss quadrature (cgx_lanczos, cgx_trace_slq; cgx_lanczos.hip) -----------
 // Up to kMaxRhs three-term recurrences side by side, blocks laid out as the multi kernels' (column j at base + j * lda, zero padded
 // up to lda).  A step is the plain K1m (launch_multi_gemv, fused = false) on the not yet normalised w, then launch_lanczos_step.

@@ -70,6 +70,29 @@ cgx_status check_shifted(cgx_ctx *ctx, int nshift, const double *sigma, const do
 
 }  // namespace
 
+// The true residuals of nshift shifted systems, enqueued: Y_j = A x_j (dense: one pass over A for all shifts; CSR: one SpMV per
+// shift), then ss->norms[j] = ||Y_j + ss->sigma[j] x_j - b||^2, ||b||^2, ||x_j||^2.
+cgx_status cgxi::shifted_residual_norms(cgx_ctx *ctx, int nshift, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
+                                        cgx::ShiftScalars *ss)
+{
+    Shard &s = ctx->shards[0];
+    hipStream_t st = ctx->stream;
+    const long lda = ctx->lda;
+    if (ctx->csr) {
+        for (int j = 0; j < nshift; ++j)
+            HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, lda, X + (size_t)j * lda, Y + (size_t)j * lda,
+                                                    s.k1_part(), st));
+    } else {
+        // always the full width kS: a row's sum order depends on the kernel width, and a shift's result must not depend on how many
+        // others there are (the columns beyond nshift hold zeros or an earlier call's x)
+        cgx::MultiArgs g = plain_k1m_args(ctx, kS, X, Y, k1p);
+        g.ms = ms;
+        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
+    }
+    HIP_TRY(ctx, cgx::launch_shift_norms(ctx->n, lda, nshift, Y, s.b_full, X, ss, st));
+    return CGX_OK;
+}
+
 extern "C" {
 
 cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res)
@@ -129,19 +152,7 @@ cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, doub
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
 
-    // the true residuals: Y_j = A x_j (dense: one pass over A for all shifts; CSR: one SpMV per shift), then the norms
-    if (ctx->csr) {
-        for (int j = 0; j < nshift; ++j)
-            HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, lda, v.X + (size_t)j * lda, v.Y + (size_t)j * lda,
-                                                    s.k1_part(), st));
-    } else {
-        // always the full width kS: a row's sum order depends on the kernel width, and a shift's result must not depend on how many
-        // others there are (the columns beyond nshift hold zeros or an earlier call's x)
-        cgx::MultiArgs g = plain_k1m_args(ctx, kS, v.X, v.Y, v.k1p);
-        g.ms = v.ms;
-        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
-    }
-    HIP_TRY(ctx, cgx::launch_shift_norms(n, lda, nshift, v.Y, s.b_full, v.X, v.ss, st));
+    CGX_TRY(shifted_residual_norms(ctx, nshift, v.X, v.Y, v.k1p, v.ms, v.ss));
     cgx::ShiftScalars hs;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ss, sizeof hs, hipMemcpyDeviceToHost, st));
     CGX_TRY(download_columns(ctx, X, ldx, v.X, nshift));

@@ -77,6 +77,16 @@ void CGSolver::solve_shifted(const std::vector<double> &shifts, std::vector<doub
     if (ns) m_result = m_shift_results[0];
 }
 
+void CGSolver::solve_minres(const std::vector<double> &shifts, std::vector<double> &X)
+{
+    const size_t ns = shifts.size(), nn = static_cast<size_t>(n());
+    X.assign(ns * nn, 0.0);
+    m_shift_results.assign(ns, cgx_result{});
+    check(cgx_solve_minres(m_ctx, static_cast<int>(ns), shifts.data(), X.data(), static_cast<long>(nn), m_shift_results.data()),
+          "solve_minres");
+    if (ns) m_result = m_shift_results[0];
+}
+
 void CGSolver::solve(double *x, int /*NUM_THREADS*/, int /*BLOCK_WIDTH*/, bool /*T*/)
 {
     std::vector<double> xv(static_cast<size_t>(n()), 0.0);   // fill<<<>>>(m_n, x, 0.0), code/CUDA/cg.cu:217

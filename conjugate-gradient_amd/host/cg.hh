@@ -53,6 +53,9 @@ public:
     /// multi-shift CG (include/cgx.h cgx_solve_shifted): X[j * n() + i] = solution i of (A + shifts[j] I) x = b from a zero guess,
     /// one pass over A per iteration for all shifts; the per-shift results are kept (shift_results), last_result() is shift 0's
     void solve_shifted(const std::vector<double> &shifts, std::vector<double> &X);
+    /// MINRES (include/cgx.h cgx_solve_minres): the same layout and results for shifts of either sign and a symmetric A that need
+    /// not be definite
+    void solve_minres(const std::vector<double> &shifts, std::vector<double> &X);
     const std::vector<cgx_result> &shift_results() const { return m_shift_results; }
     const cgx_result &last_result() const { return m_result; }
     int rank() const { return m_cfg.rank; }

@@ -20,6 +20,8 @@
 // `--shifts s0,s1,...` (NOT a reference mode) runs multi-shift CG instead of the plain solve (include/cgx.h cgx_solve_shifted): the
 // systems (A + s_j I) x = b for up to 16 shifts s_j >= 0 from one Krylov sequence, one pass over A per iteration.  The timing line
 // in OUTFILE is written as ever; one line per shift follows on stdout.  One GPU, dense or --csr, no --jacobi.
+// `--minres s0,s1,...` (NOT a reference mode) runs MINRES instead (include/cgx.h cgx_solve_minres): the same systems for up to 16
+// shifts of either sign and a symmetric matrix that need not be definite; arguments and output as --shifts.  Not with --shifts.
 // `--pivchol K [--pivchol-shift D]` (NOT a reference mode) solves with the rank-K pivoted-Cholesky preconditioner plus shift
 // (include/cgx.h CGX_PRECOND_PIVCHOL; D = 0 or absent: the automatic shift): one GPU, dense storage, not with --jacobi.
 // `--logdet P[,M]` (NOT a reference mode) estimates log det of the matrix instead of solving (include/cgx.h cgx_trace_slq): stochastic
@@ -172,6 +174,9 @@ int usage(const char *prog)
               << "         --shifts s0,s1,...       opt-in, not in the reference: solve (A + s I) x = b for up to 16 shifts s >= 0 in\n"
               << "                                  one Krylov sequence (multi-shift CG) instead of the plain solve; one GPU, dense\n"
               << "                                  or --csr, not with --jacobi; prints one line per shift\n"
+              << "         --minres s0,s1,...       opt-in, not in the reference: the same by MINRES, for shifts of either sign and a\n"
+              << "                                  symmetric matrix that need not be definite; one GPU, dense or --csr, not with\n"
+              << "                                  --jacobi or --shifts; prints one line per shift\n"
               << "         --logdet P[,M]           opt-in, not in the reference: estimate log det A instead of solving, by stochastic\n"
               << "                                  Lanczos quadrature with P probes (1 ... 256) of M steps (default 100); one GPU,\n"
               << "                                  dense storage, no preconditioner, not with --shifts; prints one line\n"
@@ -210,6 +215,7 @@ int main(int argc, char **argv)
     bool have_pivchol_shift = false;
     std::vector<double> shifts;
     bool shifted = false;
+    bool minres = false;                                     // --minres: the list is in `shifts`, and `shifted` is set as well
     int logdet_probes = 0, logdet_steps = 100;   // --logdet P[,M] (0 probes: off)
     int logdet_pc_probes = 0, logdet_pc_steps = 30;   // --logdet-pc P[,M] (0 probes: off)
     int apply_fn = -1, apply_steps = 100;        // --apply NAME[,M[,T]] (-1: off)
@@ -247,15 +253,20 @@ int main(int argc, char **argv)
                 return usage(argv[0]);
             }
         }
-        else if (a == "--shifts" && i + 1 < argc) {
+        else if ((a == "--shifts" || a == "--minres") && i + 1 < argc) {
+            if (shifted) {
+                std::cerr << argv[0] << ": --shifts and --minres are two solvers: give one of them, once\n";
+                return usage(argv[0]);
+            }
             shifted = true;
+            minres = a == "--minres";
             std::stringstream list(argv[++i]);
             std::string item;
             while (std::getline(list, item, ',')) {
                 char *end = nullptr;
                 const double v = strtod(item.c_str(), &end);
                 if (item.empty() || *end != '\0') {
-                    std::cerr << argv[0] << ": --shifts takes a comma-separated list of numbers, not '" << item << "'\n";
+                    std::cerr << argv[0] << ": " << a << " takes a comma-separated list of numbers, not '" << item << "'\n";
                     return usage(argv[0]);
                 }
                 shifts.push_back(v);
@@ -630,6 +641,7 @@ int main(int argc, char **argv)
                                &eig_done, &eig_found) != CGX_OK)
                 throw std::runtime_error(std::string("--eigs: ") + cgx_last_error(solver.context()));
         }
+        else if (minres) solver.solve_minres(shifts, x_shifted);
         else if (shifted) solver.solve_shifted(shifts, x_shifted);
         else if (cuda_form) solver.solve(x_d.data(), legacy_nt, legacy_bw, legacy_t);
         else solver.solve(x_d);
@@ -670,7 +682,7 @@ int main(int argc, char **argv)
                 const std::vector<cgx_result> &sr = solver.shift_results();
                 for (size_t j = 0; j < sr.size(); ++j)
                     std::cout << "\t[SHIFT " << shifts[j] << "] iterations = " << sr[j].iterations << ", converged = " << sr[j].converged
-                              << ", residual = " << std::scientific << sr[j].residual_prev << ", ||(A + sI)x - b||/||b|| = "
+                              << ", residual = " << std::scientific << (minres ? sr[j].residual_last : sr[j].residual_prev) << ", ||(A + sI)x - b||/||b|| = "
                               << sr[j].rel_residual << std::defaultfloat << std::endl;
             }
             if (stats) {

@@ -381,6 +381,37 @@ cgx_status  cgx_probe_gemv_multi(cgx_ctx *ctx, int nrhs, const double *P, long l
 #define CGX_MAX_SHIFTS 16
 cgx_status  cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res);
 
+/* ---- symmetric indefinite and negatively shifted systems: MINRES (one pass over A per iteration serves all shifts) ---- */
+/* MINRES (Paige and Saunders 1975): (A + sigma[j] I) x_j = b for nshift finite shifts sigma[j] of any sign
+ * and size.  A is the current matrix, taken as symmetric and not checked; it need not be definite, and neither need A + sigma I.
+ * b is the current source term.  The Lanczos recurrence from r0 = b does not depend on the shift, so one plain K1 launch per
+ * iteration (any per-launch plan: general dense, the symmetric upper-triangle kernel, CSR; also where the context's plan is a
+ * persistent kernel: that plan is left as it is and the next cgx_solve uses it again) serves every shift, and a shift costs three
+ * Givens rotations on scalars and two vector updates per iteration (csrc/cgx_minres.hip).  The initial guess is zero for every
+ * shift (one Krylov space from r0 = b serves all shifts): X is output only, one solution per ROW, X[j*ldx + i] -- the sign
+ * convention and the argument layout of cgx_solve_shifted, so a caller can switch between the two.
+ * Iteration k (0-based) applies column k of the Lanczos matrix; phibar_(k+1), the recurrence's residual norm behind it, falls
+ * monotonically and is ||(A + sigma_j I) x_j - b|| in exact arithmetic.  Shift j is frozen in iteration k -- converged = 1,
+ * iterations = k, residual_last = |phibar_(k+1)|, residual_prev = |phibar_k|, nothing writes its x afterwards -- when
+ * |phibar_(k+1)| < tol (cgx_set_tolerance, absolute, as everywhere).  A Lanczos breakdown in step t (beta_(t+1) <= 2^-36 max
+ * |alpha|, cgx_lanczos's rule: the Krylov space is invariant) ends the recurrence: a running shift whose diagonal entry in front
+ * of the last rotation is <= 2^-36 (max |alpha| + |sigma_j|) is singular on that space, keeps the x it had and reports converged
+ * = 0, iterations = t; every other running shift takes the column and ends with converged = 1, iterations = t, residual_last =
+ * 0.  A shift whose rotation or step length is not finite is frozen unconverged without an update of x.  The loop ends, decided
+ * on the device and found by the check_every poll, when every shift is frozen, at a breakdown, or after max_iter iterations (the
+ * shifts still running: converged = 0, iterations = max_iter, both residuals those of the last two columns).
+ * res: nshift results (may be NULL): x_norm = ||x_j||, rel_residual = the true ||(A + sigma_j I) x_j - b|| / ||b|| from a final
+ * product as cgx_solve_shifted makes it, seconds_solve and seconds_loop, gemv_bytes that of the single K1; gemv_ms_* and the
+ * launch counts stay 0, because plain K1 launches are not event-timed.  The result of shift j depends on (A, b, sigma_j, tol,
+ * max_iter, the K1 plan) only: not on the other shifts, their number or order, the kernel width, or check_every; shifts may repeat.
+ * One GPU (CGX_COMM_SELF), dense or CSR storage.  CGX_ERR_UNSUPPORTED: more than one rank or CGX_COMM_LOOPBACK, banded storage,
+ * a preconditioner set (it would be ignored), gemv_variant 40000 / 50000.  CGX_ERR_BAD_ARG: a null pointer, nshift outside
+ * 1 .. CGX_MAX_MINRES_SHIFTS, ldx < n, a shift that is not finite (its index in cgx_last_error), no matrix or no source term, an
+ * open cgx_solve_begin / cgx_solve_end pair.  A failed call leaves the context usable and X as it was; a later cgx_solve,
+ * cgx_solve_multi or cgx_solve_shifted gives the bits it gave before. */
+#define CGX_MAX_MINRES_SHIFTS 16
+cgx_status  cgx_solve_minres(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res);
+
 /* ---- Lanczos quadrature: log det A, tr(A^-1) and spectrum estimates of the current matrix ---- */
 /* The symmetric Lanczos three-term recurrence from nvec start vectors at once, one pass over A per step for all of them
  * (csrc/cgx_lanczos.hip; the mat-vec is cgx_solve_multi's plain multi-vector K1).  Per start vector j:
