@@ -145,7 +145,8 @@ cgx_status cgx_solve_minres(cgx_ctx *ctx, int nshift, const double *sigma, doubl
             o = base;
             const bool frozen = hm.frozen_at[j] != cgx::kMinresLive;
             o.iterations = frozen ? hm.frozen_at[j] : k;
-            o.converged = frozen ? hm.conv[j] : 0;
+            // max_iter = 0: no launch ran, so nothing on the device looked at b; b = 0 is solved by x = 0 as it is in launch 0
+            o.converged = frozen ? hm.conv[j] : (k == 0 && hs.norms[j][1] == 0.0 ? 1 : 0);
             o.residual_prev = hm.res_prev[j];
             o.residual_last = hm.res_last[j];
             o.x_norm = std::sqrt(hs.norms[j][2]);

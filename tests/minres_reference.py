@@ -18,6 +18,19 @@ import long_vector_reference as lv
 
 BREAK = 2.0 ** -36
 
+# The 16 shifts of the long-vector run (tests/test_gpu_minres_edges.py; lap2d, b = long_vector_reference.normal_b, 12 columns at
+# tol 1e-6): 100, -20, -1e4, 30, 1e3, 200, -50 and 3e4 freeze on the way, the others run out.  tests/test_minres_abi.py pins that
+# no shift's residual_last lies in [0.7 tol, 1.5 tol] and no residual_prev of a frozen one below 1.05 tol.
+LONG_SHIFTS = [0.0, 1.0, -1.0, 100.0, -3.7, -20.0, -1e4, 30.0, 1e3, 0.5, -0.25, 200.0, -50.0, 2.5, 3e4, -6.0]
+LONG_TOL = 1e-6
+
+
+def tile_shifts(n):
+    """The shifts of the symmetric hash matrix with a zero diagonal at the sizes past 256 K1 partials: its spectral radius is about
+    r = 2 sqrt(n / 3), so +-r/2 lie inside the spectrum, +-3r/2 and 1e4 outside, and no eigenvalue has to be computed."""
+    r = 2.0 * np.sqrt(n / 3.0)
+    return [0.0, 1.0, -1.0, 0.5 * r, -0.5 * r, 1.5 * r, -1.5 * r, 1e4]
+
 
 def operator(A, dtype):
     """x -> A x for a dense array, a CSR triple (indptr, indices, data) or a callable (taken as it is)."""
@@ -68,7 +81,8 @@ def minres(A, b, sigmas, max_iter, tol=0.0, dtype=np.float64):
             gbar = q["sn"] * q["dbar"] - q["cs"] * alfa
             eps_old = q["eps"]
             q["eps"], q["dbar"] = q["sn"] * bn, -q["cs"] * bn
-            gamma = np.sqrt(gbar * gbar + bn * bn)
+            with np.errstate(over="ignore"):        # |sigma| of 1e155 and more: gamma = inf, and the shift freezes below
+                gamma = np.sqrt(gbar * gbar + bn * bn)
             if breakdown and abs(gbar) <= brk * (amax + abs(q["sigma"])):   # singular on the Krylov space: x stays
                 q["residual_prev"] = q["residual_last"] = abs(q["phibar"])
                 freeze(q, t, 0)

@@ -12,7 +12,7 @@ storage do not show the pitch; there it is asserted on a dense context made with
 Address audit at lda == n (n % 16 == 0), and lda == n + 1 ... n + 15 for the other n (lda is always even, so an odd n has at least
 one pad element).  Allocations: A rows * lda; p[0], p[1], dinv lda; r lda + G (G = update_xr_grid(n) r.r partials behind it); z
 lda + 2 G; Ap segment Sr = roundup(rows, 2) plus a tail; W block * lda; L rank * lda; symmetric slots nb * lda; the multi and shift
-blocks 16 * lda per vector (cgx_context.cpp, cgx_precond.cpp, cgx_multi_host.cpp, cgx_shift_host.cpp).
+blocks 16 * lda per vector (cgx_context.cpp, cgx_precond.cpp, cgx_multi_host.cpp, cgx_shift_host.cpp, cgx_minres_host.cpp).
 
   kernel                    access                                  bound            why it holds
   k_gemv_colsplit           v, r, p_new, A row + c, c + 1           c + 1 < ncols    ncols = min(roundup(n, 2), lda); c is even
@@ -28,6 +28,11 @@ blocks 16 * lda per vector (cgx_context.cpp, cgx_precond.cpp, cgx_multi_host.cpp
   k_multi_gemv              V, R, P at j * lda + col, col + 1       col + 1 < roundup(n, 2) <= lda   live columns only
   k_multi_update / _init    j * lda + i                             i < n            guarded
   k_shift_update / _begin   X, P at j * lda + i                     i < n (begin: i < lda)   guarded, j < nshift
+  k_minres_init             w, vprev at i; X, D[0], D[1] at j * lda + i   i < lda, j < nshift   the side block of cgx_minres_host.cpp: X,
+                                                                                     D[0], D[1], Y 16 * lda each, two vectors of lda, end to
+                                                                                     end; b[i] is read for i < n only, rows n .. lda get 0
+  k_minres_step / _close    w, Y, vprev at i; X, D at j * lda + i   i < n, j < nshift   stores guarded, first-trip loads clamped to row 0
+                            ww_in[wg], ww_out[wg]                   wg < G           and to shift 0; the partials have their own 2 G doubles
   k_symv_tiles              v, r, p_new at c, c + 1; A row + col    c + 1 < ncols    vec2 guards, col clamped to ncols - 2
                             parts[J * lda + i]                      i < n, J < nb    guarded
   k_symv_fold               parts[s * lda + rc], p[rc], rc + 1      rc + 1 < roundup(n, 2) <= lda   row n of an odd n lies in the
@@ -48,6 +53,7 @@ import test_gpu_banded as tb
 import test_gpu_block_jacobi as bj
 import test_gpu_csr as tc
 import test_gpu_jacobi_scaled as js
+import test_gpu_minres as mn
 import test_gpu_multi_rhs as mr
 import test_gpu_parity as tp
 import test_gpu_pivchol as pv
@@ -419,6 +425,36 @@ def test_solve_shifted_without_pad_elements(gpu_pkg, oracle, storage):
     same_solve((x, r), (x16, r16), storage)
     for j in range(16):
         same_solve((X[j], res[j]), (X16[j], res16[j]), (storage, j))
+
+
+def _solve_minres(pkg, oracle, kind, n, storage, pad):
+    _, _, S = mn._problem(oracle, kind, n)
+    with mn._solver(pkg, oracle, kind, n, storage, lda_pad=pad) as s:
+        if storage == "dense":
+            assert_pitch(s, n, pad)
+        s.set_max_iter(ITERS)
+        s.tolerance(0.0)
+        return s.solve_minres(S)
+
+
+# lda == n and 256 K1 partials (the first load slot of fold_pap exactly full) | one pad element | lda == n on CSR
+@pytest.mark.parametrize("kind,n,storage", [("hash0", 1024, "dense"), ("hash0", 1023, "dense"), ("lap2d", 1008, "csr")])
+def test_solve_minres_without_pad_elements(gpu_pkg, oracle, kind, n, storage):
+    """cgx_solve_minres with 8 shifts of both signs: the sixteen lda-long columns of X, D[0], D[1] and Y and the two recurrence
+    vectors of its side block lie end to end, and k_minres_init writes rows n .. lda - 1 of each.  tests/test_gpu_minres.py's bars
+    against tests/minres_reference.py, and the default pitch's bits: the rows behind n hold exact zeros at every pitch."""
+    assert pitch(n, 0) == n16(n) and (n % 16 == 0 or pitch(n, 0) == n + 1)
+    if storage == "csr":
+        assert_pitch_on_dense_twin(gpu_pkg, n, 0)
+    A, b, S = mn._problem(oracle, kind, n)
+    assert len(S) == 8
+    X, res = _solve_minres(gpu_pkg, oracle, kind, n, storage, 0)
+    absA = np.abs(A)
+    mn._check_against_reference(X, res, mn._reference(oracle, kind, n, S, ITERS, 0.0), lambda x: A @ x, lambda x: absA @ x, b, S, ITERS,
+                                6 if kind == "lap2d" else n, "minres pad 0 %s n=%d %s" % (kind, n, storage))
+    X16, res16 = _solve_minres(gpu_pkg, oracle, kind, n, storage, DEFAULT)
+    for j in range(len(S)):
+        same_solve((X[j], res[j]), (X16[j], res16[j]), (kind, n, storage, S[j]))
 
 
 # ---- 6. the symmetric K1 (variant 6), the sparse K1s ----------------------------------------------------------------------------------------------------

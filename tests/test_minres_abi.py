@@ -1,6 +1,8 @@
 """Build-time and host-only checks of MINRES (cgx_solve_minres): the argument check without a context, the header constant and its
 Python mirror, the host reference that judges the GPU (tests/minres_reference.py) against np.linalg.solve and against its own
-long-double run, the --minres argument errors of the CLI, and the register report of every kernel in csrc/cgx_minres.hip."""
+long-double run and on every scenario of tests/test_gpu_minres_edges.py (the loop's ends on the 5-dimensional problem, shifts that
+overflow, a source term that is zero or not finite, the hash matrix past 256 K1 partials, the 16 shifts of the long-vector run),
+the --minres argument errors of the CLI, and the register report of every kernel in csrc/cgx_minres.hip."""
 import ctypes as C
 import os
 import re
@@ -104,6 +106,94 @@ def test_reference_breakdown_and_singular_shifts():
         assert np.array_equal(q["x"], p["x"])
     zero = mr.minres(np.diag(d), np.zeros(n), [1.0], n, 1e-10)[0]
     assert (zero["iterations"], zero["converged"], zero["residual_last"]) == (0, 1, 0.0) and not zero["x"].any()
+
+
+# ---- the scenarios of tests/test_gpu_minres_edges.py and the MINRES section of tests/test_gpu_row_pitch.py ---------------------------
+DIAG5_SHIFTS = [0.0, 0.5, 4.0, -2.0]
+
+
+def _diag5(n=600):
+    return np.diag(np.array([1.0, 2.0, 3.0, -4.0, -5.0])[np.arange(n) % 5]), np.ones(n)
+
+
+def _hash0(oracle, n):
+    import test_gpu_minres as mn
+    return oracle.hash_rows(n, 0, n, mn.SEED, True, 0.0), np.cos(np.arange(n, dtype=np.float64))
+
+
+def test_reference_loop_ends_on_diag5():
+    """The 5-dimensional problem cut at max_iter = 5 (the breakdown is found behind the last column), 4 (nothing breaks down: every
+    shift runs out) and 0 (nothing runs: x = 0 and both residuals are ||b||; b = 0 is solved by x = 0 and counts as converged)."""
+    A, b = _diag5()
+    full = mr.minres(A, b, DIAG5_SHIFTS, 600, 0.0)
+    five = mr.minres(A, b, DIAG5_SHIFTS, 5, 0.0)
+    for q, p in zip(five, full):
+        assert np.array_equal(q["x"], p["x"]) and all(q[k] == p[k] for k in ("iterations", "converged", "residual_prev", "residual_last"))
+    assert [(q["iterations"], q["converged"]) for q in five] == [(4, 1), (4, 1), (4, 0), (4, 0)]
+    assert five[0]["residual_last"] == five[1]["residual_last"] == 0.0
+    four = mr.minres(A, b, DIAG5_SHIFTS, 4, 0.0)
+    assert [(q["iterations"], q["converged"]) for q in four] == [(4, 0)] * 4
+    for q, want in zip(four, (4.40, 3.55, 10.95, 10.95)):
+        assert abs(q["residual_last"] - want) < 0.006 and q["residual_last"] <= q["residual_prev"], q
+    nb = float(np.linalg.norm(b))
+    for q in mr.minres(A, b, DIAG5_SHIFTS, 0, 0.0):
+        assert (q["iterations"], q["converged"], q["residual_prev"], q["residual_last"]) == (0, 0, nb, nb) and not q["x"].any(), q
+    for q in mr.minres(A, np.zeros(600), DIAG5_SHIFTS, 0, 0.0):
+        assert (q["iterations"], q["converged"], q["residual_prev"], q["residual_last"]) == (0, 1, 0.0, 0.0) and not q["x"].any(), q
+
+
+def test_reference_huge_shifts_and_infinite_source_term(oracle):
+    """sigma = +-1e200 overflows gbar^2 in column 0: gamma is not finite and the shift freezes there, unconverged, with x = 0 and
+    both residuals ||b||; the other shifts' bits do not change.  A b with an inf entry has no finite norm: nothing runs."""
+    n = 513
+    A, b = _hash0(oracle, n)
+    res = mr.minres(A, b, [0.0, 1e200, -1e200, 1.0], 12, 0.0)
+    nb = float(np.sqrt(b @ b))
+    for q in res[1:3]:
+        assert (q["iterations"], q["converged"], q["residual_prev"], q["residual_last"]) == (0, 0, nb, nb) and not q["x"].any(), q
+    for q, p in zip((res[0], res[3]), mr.minres(A, b, [0.0, 1.0], 12, 0.0)):
+        assert np.array_equal(q["x"], p["x"]) and (q["iterations"], q["converged"]) == (12, 0) == (p["iterations"], p["converged"])
+        assert q["residual_last"] == p["residual_last"] < q["residual_prev"]
+    binf = b.copy()
+    binf[n // 2] = np.inf
+    for q in mr.minres(A, binf, [0.0, -2.0], 12, 1e-10):
+        assert (q["iterations"], q["converged"]) == (0, 0) and not q["x"].any(), q
+        assert not np.isfinite(q["residual_prev"]) and not np.isfinite(q["residual_last"]), q
+
+
+@pytest.mark.parametrize("n", [1028, 2052, 4100])
+def test_reference_float64_against_longdouble_hash0(oracle, n):
+    """The indefinite hash matrix past 256 K1 partials, 12 columns, minres_reference.tile_shifts (four of them interior)."""
+    A, b = _hash0(oracle, n)
+    S = mr.tile_shifts(n)
+    lo, hi = mr.minres(A, b, S, 12, 0.0), mr.minres(A, b, S, 12, 0.0, np.longdouble)
+    for sigma, q, p in zip(S, lo, hi):
+        err = np.linalg.norm(q["x"] - p["x"]) / np.linalg.norm(p["x"])
+        print("hash0 n=%d sigma=%g: float64 against long double %.2e" % (n, sigma, err))
+        assert q["iterations"] == p["iterations"] == 12 and q["converged"] == p["converged"] == 0
+        assert err <= 1e-13, (sigma, err)
+
+
+def test_reference_long_shift_list():
+    """minres_reference.LONG_SHIFTS on lap2d at 263501 rows: float64 against long double, the same freezes in both, and no freeze
+    on the edge of the tolerance -- a device run whose |phibar| is off by 1e-9 relative freezes in the same columns."""
+    import long_vector_reference as lv
+    import test_gpu_csr as tc
+    n, tol = lv.N_LONG, mr.LONG_TOL
+    csr, b = tc.lap2d_csr(n), lv.normal_b(n)
+    lo, hi = mr.minres(csr, b, mr.LONG_SHIFTS, 12, tol), mr.minres(csr, b, mr.LONG_SHIFTS, 12, tol, np.longdouble)
+    for sigma, q, p in zip(mr.LONG_SHIFTS, lo, hi):
+        err = np.linalg.norm(q["x"] - p["x"]) / np.linalg.norm(p["x"])
+        print("long sigma=%g: (%d, %d), residual_prev %.3e, residual_last %.3e, float64 against long double %.2e" % (
+            sigma, q["iterations"], q["converged"], q["residual_prev"], q["residual_last"], err))
+        assert (q["iterations"], q["converged"]) == (p["iterations"], p["converged"]), (sigma, q, p)
+        assert err <= 1e-13, (sigma, err)
+        assert q["residual_last"] < 0.7 * tol or q["residual_last"] > 1.5 * tol, (sigma, q["residual_last"])
+        assert q["converged"] == (1 if q["residual_last"] < tol else 0) and (not q["converged"] or q["residual_prev"] > 1.05 * tol), q
+    got = {s: (q["iterations"], q["converged"]) for s, q in zip(mr.LONG_SHIFTS, lo)}
+    assert [got[s] for s in (100.0, -20.0, -1e4, 30.0, 1e3)] == [(5, 1), (9, 1), (2, 1), (7, 1), (3, 1)], got
+    assert all(got[s] == (12, 0) for s in (0.0, 1.0, -1.0, -3.7)), got
+    assert sum(c for _, c in got.values()) == 8, got
 
 
 # ---- the command line ---------------------------------------------------------------------------------------------------------------
