@@ -558,28 +558,26 @@ class CGSolver:
         self._check(lib().cgx_probe_multi_pc_apply(self._h, int(R.shape[0]), _dp(R), int(R.shape[1]), _dp(Z), int(Z.shape[1])))
         return Z
 
-    def solve_shifted(self, shifts):
-        """shifts: sigma_j >= 0 (at most MAX_SHIFTS).  Returns (X, [result dicts]), X of shape (len(shifts), n): row j solves
-        (A + sigma_j I) x = b for the current matrix and source term from a zero guess, all shifts in one Krylov sequence with
-        one pass over A per iteration (multi-shift CG, cgx_solve_shifted)."""
+    def _solve_shifts(self, entry, shifts):
         sig = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
         k, n = sig.size, self.n()
         X = np.zeros((k, n), dtype=np.float64)
         res = (Result * max(k, 1))()
-        self._check(lib().cgx_solve_shifted(self._h, int(k), _dp(sig), _dp(X), int(n), res))
+        self._check(entry(self._h, int(k), _dp(sig), _dp(X), int(n), res))
         return X, [res[j].as_dict() for j in range(k)]
+
+    def solve_shifted(self, shifts):
+        """shifts: sigma_j >= 0 (at most MAX_SHIFTS).  Returns (X, [result dicts]), X of shape (len(shifts), n): row j solves
+        (A + sigma_j I) x = b for the current matrix and source term from a zero guess, all shifts in one Krylov sequence with
+        one pass over A per iteration (multi-shift CG, cgx_solve_shifted)."""
+        return self._solve_shifts(lib().cgx_solve_shifted, shifts)
 
     def solve_minres(self, shifts):
         """shifts: finite sigma_j of either sign (at most MAX_MINRES_SHIFTS).  Returns (X, [result dicts]), X of shape
         (len(shifts), n): row j solves (A + sigma_j I) x = b for the current matrix, taken as symmetric (it need not be definite),
         and source term from a zero guess, all shifts on one Lanczos recurrence with one pass over A per iteration (MINRES,
         cgx_solve_minres)."""
-        sig = np.ascontiguousarray(shifts, dtype=np.float64).reshape(-1)
-        k, n = sig.size, self.n()
-        X = np.zeros((k, n), dtype=np.float64)
-        res = (Result * max(k, 1))()
-        self._check(lib().cgx_solve_minres(self._h, int(k), _dp(sig), _dp(X), int(n), res))
-        return X, [res[j].as_dict() for j in range(k)]
+        return self._solve_shifts(lib().cgx_solve_minres, shifts)
 
     def lanczos(self, V0, steps):
         """V0: float64 array (k, n), one start vector per row (k <= MAX_RHS).  Returns (alpha, beta, steps_done): the coefficients

@@ -239,7 +239,7 @@ __global__ __launch_bounds__(kCombineThreads) void k_eigs_combine(int n, long ld
         if (j < nev) X[(size_t)j * (size_t)ldx + (size_t)i] = i < n ? acc[j] : 0.0;
 }
 
-// One workgroup per vector: out[j] = || Y_j - theta_j X_j ||^2 in a fixed order (the shape of k_multi_norms).
+// One workgroup per vector: out[j] = || Y_j - theta_j X_j ||^2 in a fixed order (the shape of k_column_norms, cgx_multi.hip).
 __global__ __launch_bounds__(1024) void k_eigs_residual(int n, long lda, const double *__restrict__ Y, const double *__restrict__ X,
                                                         const double *__restrict__ theta, double *__restrict__ out)
 {

@@ -370,12 +370,25 @@ cgx_status check_one_gpu_call(cgx_ctx *ctx, const std::string &fn);
 // A side block of the context (cgx_ctx::multi, cgx_ctx::shift): allocated and zeroed on first use, freed again if that fails.
 cgx_status ensure_side_block(cgx_ctx *ctx, double **block, size_t *block_bytes, size_t bytes);
 
-// cgx_shift_host.cpp: the true residuals of nshift shifted systems (cgx_solve_shifted, cgx_solve_minres), enqueued on the context's
-// stream.  X, Y: kMaxShifts x lda blocks (shift j at + j * lda); Y_j = A x_j -- dense: one multi-vector pass at full width with
-// k1p / ms as its partials and scalar block, CSR: one SpMV per shift -- then ss->norms[j] = ||Y_j + ss->sigma[j] x_j - b||^2,
-// ||b||^2, ||x_j||^2.
-cgx_status shifted_residual_norms(cgx_ctx *ctx, int nshift, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
-                                  cgx::ShiftScalars *ss);
+// THE verification of the k-column solves (cgx_solve_multi / _multi_pc / _shifted / _minres), enqueued on the context's stream: the
+// true residuals of ncol systems.  X, Y: kMaxRhs x lda blocks (column j at + j * lda); Y_j = A x_j -- dense: one plain K1m pass
+// over `width` columns with k1p / ms as its partials and scalar block, CSR: one SpMV per column -- then norms[3 j ...] =
+// ||Y_j + sigma_j x_j - b_j||^2, ||b_j||^2, ||x_j||^2 (launch_column_norms: b_j = b + j * ldb; sigma: host array, or nullptr).
+cgx_status column_residual_norms(cgx_ctx *ctx, int ncol, int width, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
+                                 const double *b, long ldb, const double *sigma, double *norms);
+// ... and THE filler of their results: one cgx_result per column from the two wall times, gemv_bytes, the K1 statistics (k1_stats;
+// else they stay 0), the host copy of those norms (x_norm, rel_residual) and what only the solve knows of column j.
+struct ColumnOutcome {
+    int iterations, converged;
+    double residual_prev, residual_last;
+};
+void fill_column_results(const cgx_ctx *ctx, cgx_result *res, int ncol, double t_begin, double t_loop, double gemv_bytes, bool k1_stats,
+                         const double (*norms)[3], const std::function<ColumnOutcome(int)> &outcome);
+// The refusals of cgx_solve_shifted and cgx_solve_minres in the order check_multi (cgx_multi_host.cpp) makes them: context, problem,
+// transport and storage, arguments.  limit: the name of the bound on nshift; negative_ok: shifts of either sign; precond / form:
+// what the message about a preconditioner says, and which form the persistent kernels lack.
+cgx_status check_shift_call(cgx_ctx *ctx, const char *name, const char *limit, bool negative_ok, const char *precond, const char *form,
+                            int nshift, const double *sigma, const double *X, long ldx);
 
 // ... and one that grows (cgx_ctx::funm, cgx_ctx::eigs): made on first use, made again when a call needs more than it holds.
 // detail: what the out-of-memory message says the bytes are for.

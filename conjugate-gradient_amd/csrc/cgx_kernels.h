@@ -485,6 +485,16 @@ hipError_t launch_loopback_gather(double *const *gathered_ptrs, const Scalars *c
 // Blocks of vectors are column-major at pitch lda (column j at base + j * lda, zero padded up to lda).  nrhs columns run in the
 // kernels of width multi_width(nrhs) (1, 2, 4, 8 or 16); columns nrhs .. width-1 are masked by nrhs.
 constexpr int kMaxRhs = 16;   // = CGX_MAX_RHS
+// One double per column, by value into a kernel: the shifts of cgx_solve_shifted / cgx_solve_minres (the rest stays 0).
+struct ColumnSigmas {
+    double v[kMaxRhs];
+};
+inline ColumnSigmas column_sigmas(const double *sigma, int count)
+{
+    ColumnSigmas sg{};
+    for (int j = 0; j < count; ++j) sg.v[j] = sigma[j];
+    return sg;
+}
 struct MultiScalars {
     double rs[kMaxRhs][2];     // per column: rs[j][k & 1] is rsold of iteration k (as Scalars::rs)
     int    done[kMaxRhs];      // the column took the break (cg.cc:120-121); nothing writes its x, r, p or scalars afterwards
@@ -492,7 +502,7 @@ struct MultiScalars {
     int    all_done;           // every column has broken: the host polls this word; later kernels exit at once
     int    k_all;
     int    pad[2];
-    double norms[kMaxRhs][3];  // ||Ax - b||^2, ||b||^2, ||x||^2 per column (cg.cc:146-151)
+    double norms[kMaxRhs][3];  // ||Ax - b||^2, ||b||^2, ||x||^2 per column (cg.cc:146-151; launch_column_norms)
 };
 struct MultiArgs {
     const double *A;
@@ -529,11 +539,15 @@ hipError_t launch_multi_gemv(const MultiArgs &g, bool fused, hipStream_t s, hipE
 // K3m: for every live column x += alpha p, r -= alpha Y, r.r partials (grid multi_update_grid(n) x nrhs).
 hipError_t launch_multi_update(int n, long lda, int nrhs, const double *p, const double *Y, const double *partials, int g1, double *x,
                                double *r, double *rrp, MultiScalars *ms, int parity, hipStream_t s);
-// r = B - Y and r.r partials (set-up); the head of iteration k alone (the loop ran out); the end-of-solve norms.
+// r = B - Y and r.r partials (set-up); the head of iteration k alone (the loop ran out).
 hipError_t launch_multi_init(int n, long lda, int nrhs, const double *b, const double *Y, double *r, double *rrp, hipStream_t s);
 hipError_t launch_multi_close(MultiScalars *ms, const double *rrp, int n, int nrhs, int k, double tol, hipStream_t s);
-hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const double *b, const double *x, MultiScalars *ms,
-                              hipStream_t s);
+// THE end-of-solve norms of every k-column solve (cg.cc:146-151), behind the plain K1m pass (or the SpMVs) that left Y_j = A x_j:
+// norms[3 j ...] = ||Y_j + sigma_j x_j - b_j||^2, ||b_j||^2, ||x_j||^2 for j < ncol, one workgroup per column, fixed order.  b_j is
+// b + j * ldb: ldb = lda for a block of right-hand sides, 0 for one source term shared by all shifts.  sigma: ncol host doubles,
+// or nullptr: the kernel without the sigma term (not the same as sigma = 0 where x is not finite).
+hipError_t launch_column_norms(int n, long lda, int ncol, const double *Y, const double *X, const double *b, long ldb,
+                               const double *sigma, double *norms, hipStream_t s);
 
 // ---- several right-hand sides with a preconditioner (cgx_solve_multi_pc, cgx_multi_pc.hip) ----------------
 // Every column runs the recurrence of section 11 on the blocks above plus Z = M^-1 R.  MultiScalars keeps its layout: rs[j][] holds
@@ -583,7 +597,7 @@ struct ShiftScalars {
     double alpha[3], beta[3];      // the seed's alpha_m, beta_m at [(m + 1) % 3] (alpha_-1 = 1, beta_-1 = 0)
     double res_last[kMaxShifts];   // |zeta_(k+1)| sqrt(r_(k+1).r_(k+1)) of the shift's last iteration k
     double res_prev[kMaxShifts];   // |zeta_k| sqrt(r_k.r_k)
-    double norms[kMaxShifts][3];   // ||(A + sigma I) x - b||^2, ||b||^2, ||x||^2 (launch_shift_norms)
+    double norms[kMaxShifts][3];   // ||(A + sigma I) x - b||^2, ||b||^2, ||x||^2 (launch_column_norms)
     int    frozen_at[kMaxShifts];  // the iteration that froze the shift (kShiftLive: running).  An iteration number, not a flag:
                                    // workgroup 0 of launch k writes k while the others still read, and both values mean "runs in k"
     int    all_at;                 // the iteration that ended the loop (every shift frozen, or the seed broke); launches of later
@@ -613,9 +627,6 @@ hipError_t launch_shift_begin(int n, long lda, int nshift, const double *sigma, 
 hipError_t launch_shift_update(const ShiftArgs &a, hipStream_t s);
 // The loop ran out after k iterations: residual_prev of the shifts still running (k == 0: sqrt(r0.r0) from the partials).
 hipError_t launch_shift_close(ShiftScalars *ss, const double *rrp, int nrr, int nshift, int k, hipStream_t s);
-// norms[j] = ||Y_j + sigma_j x_j - b||^2, ||b||^2, ||x_j||^2 with Y_j = A x_j, one workgroup per shift, fixed order.
-hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, const double *b, const double *X, ShiftScalars *ss,
-                              hipStream_t s);
 
 // ---- MINRES: (A + sigma_j I) x_j = b for up to kMaxMinresShifts shifts of either sign, A symmetric (cgx_minres.hip) -----------
 // One Lanczos recurrence from r0 = b serves every shift.  Launch t is the plain K1 of the shard's plan on
@@ -623,6 +634,8 @@ hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, cons
 // X and D[2] (the x of the shifts and their last two search directions) are column-major at pitch lda like the shift block.
 constexpr int kMaxMinresShifts = 16;           // = CGX_MAX_MINRES_SHIFTS
 constexpr int kMinresLive = 0x7fffffff;        // frozen_at / end_at of a shift / a loop that is still running
+static_assert(kMaxShifts == kMaxRhs && kMaxMinresShifts == kMaxRhs,
+              "ColumnSigmas carries the shifts, and their verification runs the multi-vector K1 at full width");
 struct MinresScalars {
     int    done;                   // the two words the host polls: raised with end_at
     int    end_at;                 // the launch that ended the loop (every shift frozen, or a breakdown); later launches exit at once
@@ -653,9 +666,9 @@ struct MinresArgs {
     int t;                         // the close kernel: the launches that were enqueued
     double tol;
 };
-// w_0 = b and v_-1 = 0 (zero padded up to lda), x_j = d_j = 0 for j < nshift, the ||b||^2 partials, the scalar block, and sigma /
-// zeroed norms in the block launch_shift_norms takes behind the loop (sigma: host array).
-hipError_t launch_minres_init(const MinresArgs &a, const double *sigma, const double *b, ShiftScalars *vs, hipStream_t s);
+// w_0 = b and v_-1 = 0 (zero padded up to lda), x_j = d_j = 0 for j < nshift, the ||b||^2 partials and the scalar block (sigma:
+// host array).
+hipError_t launch_minres_init(const MinresArgs &a, const double *sigma, const double *b, hipStream_t s);
 // Behind K1 of launch t: beta_t, alpha_t, the breakdown test, column t - 1 of every running shift (x update, freeze, loop end),
 // v_t, w_(t+1) and its ||.||^2 partials.
 hipError_t launch_minres_step(const MinresArgs &a, hipStream_t s);

@@ -214,11 +214,8 @@ __global__ __launch_bounds__(256) void k_minres_step(MinresArgs a)
     if (tid == 0) a.ww_out[blockIdx.x] = nw;
 }
 
-struct MinresSigmas {
-    double v[kMaxMinresShifts];
-};
 // The grid of the step kernel, so that the ||b||^2 partials are the ones its launch 0 folds.
-__global__ __launch_bounds__(256) void k_minres_init(MinresArgs a, MinresSigmas sg, const double *__restrict__ b, ShiftScalars *vs)
+__global__ __launch_bounds__(256) void k_minres_init(MinresArgs a, ColumnSigmas sg, const double *__restrict__ b)
 {
     __shared__ double lds[4];
     double bb = 0.0;
@@ -239,10 +236,7 @@ __global__ __launch_bounds__(256) void k_minres_init(MinresArgs a, MinresSigmas 
     if (blockIdx.x == 0 && threadIdx.x < kMaxMinresShifts) {
         const int j = threadIdx.x;
         MinresScalars *ms = a.ms;
-        const double sig = j < a.nshift ? sg.v[j] : 0.0;
-        ms->sigma[j] = sig;
-        vs->sigma[j] = sig;
-        for (int q = 0; q < 3; ++q) vs->norms[j][q] = 0.0;
+        ms->sigma[j] = j < a.nshift ? sg.v[j] : 0.0;
         for (int q = 0; q < 2; ++q) {
             ms->cs[q][j] = -1.0;
             ms->sn[q][j] = ms->dbar[q][j] = ms->eps[q][j] = ms->phibar[q][j] = 0.0;
@@ -308,12 +302,10 @@ bool args_ok(const MinresArgs &a)
 
 }  // namespace
 
-hipError_t launch_minres_init(const MinresArgs &a, const double *sigma, const double *b, ShiftScalars *vs, hipStream_t s)
+hipError_t launch_minres_init(const MinresArgs &a, const double *sigma, const double *b, hipStream_t s)
 {
     if (!args_ok(a)) return hipErrorInvalidValue;
-    MinresSigmas sg{};
-    for (int j = 0; j < a.nshift; ++j) sg.v[j] = sigma[j];
-    hipLaunchKernelGGL(k_minres_init, dim3(update_xr_grid(a.n)), dim3(256), 0, s, a, sg, b, vs);
+    hipLaunchKernelGGL(k_minres_init, dim3(update_xr_grid(a.n)), dim3(256), 0, s, a, column_sigmas(sigma, a.nshift), b);
     return hipGetLastError();
 }
 

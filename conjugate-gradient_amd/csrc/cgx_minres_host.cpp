@@ -8,16 +8,11 @@
 // (cgx_ctx::minres), made on first use and freed with the problem.
 #include "cgx_internal.h"
 
-#include <cmath>
-#include <cstring>
-#include <string>
-
 using namespace cgxi;
 
 namespace {
 
 constexpr int kS = cgx::kMaxMinresShifts;
-static_assert(kS == cgx::kMaxShifts && kS == cgx::kMaxRhs, "the verification runs the shifted solve's full-width pass");
 
 struct MinresView {
     double *X, *D[2], *Y;       // kS x lda each (shift j at + j * lda); Y: the verification's products
@@ -25,7 +20,7 @@ struct MinresView {
     double *wwp[2];             // update_xr_grid(n) each: the ||w||^2 partials, ping-pong over the launches
     double *k1p;                // dense verification: the multi-vector K1's partials (written, never read)
     cgx::MultiScalars *vm;      // ... and its scalar block (the plain form does not touch it)
-    cgx::ShiftScalars *vs;      // launch_shift_norms' block: sigma in, norms out
+    double *norms;              // 3 x kS: what launch_column_norms leaves
     cgx::MinresScalars *ms;
 };
 
@@ -43,28 +38,9 @@ size_t minres_layout(const cgx_ctx *ctx, double *base, MinresView *v)
     v->wwp[1] = c.take(g3);
     v->k1p = c.take(ctx->csr ? 0 : (size_t)kS * k1p_stride(ctx->n));
     v->vm = c.take_struct<cgx::MultiScalars>();
-    v->vs = c.take_struct<cgx::ShiftScalars>();
+    v->norms = c.take(3 * (size_t)kS);
     v->ms = c.take_struct<cgx::MinresScalars>();
     return c.bytes();
-}
-
-// The checks in check_shifted's order (cgx_shift_host.cpp): context, problem, transport and storage, arguments.
-cgx_status check_minres(cgx_ctx *ctx, int nshift, const double *sigma, const double *X, long ldx)
-{
-    const std::string fn("cgx_solve_minres");
-    CGX_TRY(check_one_gpu_call(ctx, fn));
-    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense or CSR storage only (not CGX_MATRIX_BANDED)");
-    if (ctx->precond != CGX_PRECOND_NONE)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": a preconditioner is set and would be ignored (cgx_set_preconditioner)");
-    if (ctx->res_forced)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": the persistent kernels (gemv_variant 40000 / 50000) have no MINRES form");
-    if (nshift < 1 || nshift > CGX_MAX_MINRES_SHIFTS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nshift must be 1 .. CGX_MAX_MINRES_SHIFTS");
-    if (!sigma || !X) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
-    if (ldx < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");
-    for (int j = 0; j < nshift; ++j)
-        if (!std::isfinite(sigma[j])) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": shift " + std::to_string(j) + " is not finite");
-    if (!ctx->have_b) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no source term set");
-    return CGX_OK;
 }
 
 }  // namespace
@@ -73,7 +49,8 @@ extern "C" {
 
 cgx_status cgx_solve_minres(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res)
 {
-    CGX_TRY(check_minres(ctx, nshift, sigma, X, ldx));
+    CGX_TRY(check_shift_call(ctx, "cgx_solve_minres", "CGX_MAX_MINRES_SHIFTS", true,
+                             "a preconditioner is set and would be ignored (cgx_set_preconditioner)", "MINRES", nshift, sigma, X, ldx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     MinresView v;
     CGX_TRY(ensure_side_block(ctx, &ctx->minres, &ctx->minres_bytes, minres_layout(ctx, nullptr, &v)));
@@ -106,7 +83,7 @@ cgx_status cgx_solve_minres(cgx_ctx *ctx, int nshift, const double *sigma, doubl
     };
     at_launch(0);
     a.ww_out = v.wwp[0];
-    HIP_TRY(ctx, cgx::launch_minres_init(a, sigma, s.b_full, v.vs, st));
+    HIP_TRY(ctx, cgx::launch_minres_init(a, sigma, s.b_full, st));
 
     // the loop: the step kernel raises the flag when every shift is frozen or the recurrence broke down; it is polled every
     // check_every launches, one batch kept queued, and the launches behind the end write nothing
@@ -124,35 +101,24 @@ cgx_status cgx_solve_minres(cgx_ctx *ctx, int nshift, const double *sigma, doubl
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
 
-    CGX_TRY(shifted_residual_norms(ctx, nshift, v.X, v.Y, v.k1p, v.vm, v.vs));
+    // the full width kS, as cgx_solve_shifted: a shift's result must not depend on how many others there are
+    CGX_TRY(column_residual_norms(ctx, nshift, kS, v.X, v.Y, v.k1p, v.vm, s.b_full, 0, sigma, v.norms));
     cgx::MinresScalars hm;
-    cgx::ShiftScalars hs;
+    double norms[kS][3];
     HIP_TRY(ctx, hipMemcpyAsync(&hm, v.ms, sizeof hm, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(&hs, v.vs, sizeof hs, hipMemcpyDeviceToHost, st));
+    HIP_TRY(ctx, hipMemcpyAsync(norms, v.norms, sizeof norms, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     // the last call that can fail: X is written only when the solve succeeds
     HIP_TRY(ctx, hipMemcpy2D(X, (size_t)ldx * sizeof(double), v.X, (size_t)ctx->lda * sizeof(double), (size_t)n * sizeof(double),
                              (size_t)nshift, hipMemcpyDeviceToHost));
 
-    if (res) {
-        cgx_result base;
-        memset(&base, 0, sizeof base);   // gemv_ms_* and the launch counts stay 0: plain K1 launches are not event-timed
-        base.seconds_solve = wall_now() - t_begin;
-        base.seconds_loop = t_loop;
-        base.gemv_bytes = one_gpu_gemv_bytes(ctx);
-        for (int j = 0; j < nshift; ++j) {
-            cgx_result &o = res[j];
-            o = base;
-            const bool frozen = hm.frozen_at[j] != cgx::kMinresLive;
-            o.iterations = frozen ? hm.frozen_at[j] : k;
-            // max_iter = 0: no launch ran, so nothing on the device looked at b; b = 0 is solved by x = 0 as it is in launch 0
-            o.converged = frozen ? hm.conv[j] : (k == 0 && hs.norms[j][1] == 0.0 ? 1 : 0);
-            o.residual_prev = hm.res_prev[j];
-            o.residual_last = hm.res_last[j];
-            o.x_norm = std::sqrt(hs.norms[j][2]);
-            o.rel_residual = std::sqrt(hs.norms[j][0]) / std::sqrt(hs.norms[j][1]);
-        }
-    }
+    // no K1 statistics: gemv_ms_* and the launch counts stay 0, plain K1 launches are not event-timed
+    fill_column_results(ctx, res, nshift, t_begin, t_loop, one_gpu_gemv_bytes(ctx), false, norms, [&](int j) {
+        const bool frozen = hm.frozen_at[j] != cgx::kMinresLive;
+        // max_iter = 0: no launch ran, so nothing on the device looked at b; b = 0 is solved by x = 0 as it is in launch 0
+        const int conv = frozen ? hm.conv[j] : (k == 0 && norms[j][1] == 0.0 ? 1 : 0);
+        return ColumnOutcome{frozen ? hm.frozen_at[j] : k, conv, hm.res_prev[j], hm.res_last[j]};
+    });
     return CGX_OK;
 }
 

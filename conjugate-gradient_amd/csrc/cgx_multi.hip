@@ -97,16 +97,21 @@ __global__ __launch_bounds__(kMultiThreads) void k_multi_close(MultiScalars *ms,
     }
 }
 
-// Per column j (one workgroup each): ||Y_j - b_j||^2, ||b_j||^2, ||x_j||^2 (cg.cc:146-151) in a fixed order.
-__global__ __launch_bounds__(1024) void k_multi_norms(int n, long lda, const double *__restrict__ Y, const double *__restrict__ b,
-                                                      const double *__restrict__ x, MultiScalars *ms)
+// Per column j (one workgroup each): ||Y_j + sigma_j x_j - b_j||^2, ||b_j||^2, ||x_j||^2 (cg.cc:146-151) in a fixed order; Y_j =
+// A x_j, b_j = b + j * ldb.  SHIFTED = false has no sigma term at all: fma(0, x, Y) is not Y where x is not finite.
+template <bool SHIFTED>
+__global__ __launch_bounds__(1024) void k_column_norms(int n, long lda, const double *__restrict__ Y, const double *__restrict__ X,
+                                                       const double *__restrict__ b, long ldb, ColumnSigmas sg,
+                                                       double *__restrict__ norms)
 {
     __shared__ double lds[3][16];
     const int j = blockIdx.x;
+    const double sig = sg.v[j];
+    b += (long)j * ldb;
     double e = 0.0, bb = 0.0, xx = 0.0;
     for (long i = threadIdx.x; i < n; i += 1024) {
         const long off = (long)j * lda + i;
-        const double bi = b[off], xi = x[off], d = Y[off] - bi;
+        const double bi = b[i], xi = X[off], d = SHIFTED ? fma(sig, xi, Y[off]) - bi : Y[off] - bi;
         e += d * d;
         bb += bi * bi;
         xx += xi * xi;
@@ -124,7 +129,7 @@ __global__ __launch_bounds__(1024) void k_multi_norms(int n, long lda, const dou
     if (threadIdx.x < 3) {
         double s = lds[threadIdx.x][0];
         for (int t = 1; t < 16; ++t) s += lds[threadIdx.x][t];
-        ms->norms[j][threadIdx.x] = s;
+        norms[3 * j + threadIdx.x] = s;
     }
 }
 
@@ -190,10 +195,14 @@ hipError_t launch_multi_close(MultiScalars *ms, const double *rrp, int n, int nr
     return hipGetLastError();
 }
 
-hipError_t launch_multi_norms(int n, long lda, int nrhs, const double *Y, const double *b, const double *x, MultiScalars *ms,
-                              hipStream_t s)
+hipError_t launch_column_norms(int n, long lda, int ncol, const double *Y, const double *X, const double *b, long ldb,
+                               const double *sigma, double *norms, hipStream_t s)
 {
-    hipLaunchKernelGGL(k_multi_norms, dim3(nrhs), dim3(1024), 0, s, n, lda, Y, b, x, ms);
+    if (ncol < 1 || ncol > kMaxRhs || n < 1 || lda < n) return hipErrorInvalidValue;
+    if (sigma)
+        hipLaunchKernelGGL(k_column_norms<true>, dim3(ncol), dim3(1024), 0, s, n, lda, Y, X, b, ldb, column_sigmas(sigma, ncol), norms);
+    else
+        hipLaunchKernelGGL(k_column_norms<false>, dim3(ncol), dim3(1024), 0, s, n, lda, Y, X, b, ldb, ColumnSigmas{}, norms);
     return hipGetLastError();
 }
 

@@ -170,8 +170,7 @@ cgx_status solve_multi_body(cgx_ctx *ctx, bool pre, int nrhs, const double *B, l
     else HIP_TRY(ctx, cgx::launch_multi_close(v.ms, v.rrp, n, nrhs, k, ctx->tol, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
-    HIP_TRY(ctx, cgx::launch_multi_gemv(plain_args(ctx, v, nrhs, v.X), false, st));
-    HIP_TRY(ctx, cgx::launch_multi_norms(n, lda, nrhs, v.Y, v.B, v.X, v.ms, st));
+    CGX_TRY(column_residual_norms(ctx, nrhs, nrhs, v.X, v.Y, v.k1p, v.ms, v.B, lda, nullptr, &v.ms->norms[0][0]));
     cgx::MultiScalars hs;
     cgx::MultiPcScalars hp;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ms, sizeof hs, hipMemcpyDeviceToHost, st));
@@ -180,27 +179,13 @@ cgx_status solve_multi_body(cgx_ctx *ctx, bool pre, int nrhs, const double *B, l
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
 
-    if (res) {
-        cgx_result base;
-        memset(&base, 0, sizeof base);
-        base.seconds_solve = wall_now() - t_begin;
-        base.seconds_loop = t_loop;
-        fill_k1_stats(ctx, &base);
-        base.gemv_bytes = 8.0 * ((double)n * n + 2.0 * nrhs * n);
-        for (int j = 0; j < nrhs; ++j) {
-            cgx_result &o = res[j];
-            o = base;
-            const bool done = hs.done[j] != 0;
-            const int k_exit = done ? hs.k_final[j] : k;
-            const double *rr = pre ? hp.rr[j] : hs.rs[j];               // pre: rs[] holds r.z, the report is sqrt(r.r)
-            o.iterations = k_exit;
-            o.converged = done ? 1 : 0;
-            o.residual_prev = std::sqrt(rr[k_exit & 1]);                // sqrt(rsold) as printed, cg.cc:152-153
-            o.residual_last = done ? std::sqrt(rr[(k_exit + 1) & 1]) : o.residual_prev;
-            o.x_norm = std::sqrt(hs.norms[j][2]);
-            o.rel_residual = std::sqrt(hs.norms[j][0]) / std::sqrt(hs.norms[j][1]);
-        }
-    }
+    fill_column_results(ctx, res, nrhs, t_begin, t_loop, 8.0 * ((double)n * n + 2.0 * nrhs * n), true, hs.norms, [&](int j) {
+        const bool done = hs.done[j] != 0;
+        const int k_exit = done ? hs.k_final[j] : k;
+        const double *rr = pre ? hp.rr[j] : hs.rs[j];                   // pre: rs[] holds r.z, the report is sqrt(r.r)
+        const double prev = std::sqrt(rr[k_exit & 1]);                  // sqrt(rsold) as printed, cg.cc:152-153
+        return ColumnOutcome{k_exit, done ? 1 : 0, prev, done ? std::sqrt(rr[(k_exit + 1) & 1]) : prev};
+    });
     return CGX_OK;
 }
 

@@ -168,10 +168,7 @@ __global__ __launch_bounds__(256) void k_shift_update(ShiftArgs a)
 
 // x_j = 0 and p_j = r0 = b for j < nshift (rows n .. lda-1 zero), the scalar block of iteration 0: zeta_-1 = zeta_0 = 1,
 // alpha_-1 = 1, beta_-1 = 0.
-struct ShiftSigmas {
-    double v[kMaxShifts];
-};
-__global__ __launch_bounds__(256) void k_shift_begin(int n, long lda, int nshift, ShiftSigmas sg, const double *__restrict__ b,
+__global__ __launch_bounds__(256) void k_shift_begin(int n, long lda, int nshift, ColumnSigmas sg, const double *__restrict__ b,
                                                      double *__restrict__ X, double *__restrict__ P, ShiftScalars *ss)
 {
     for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < lda; i += (long)gridDim.x * 256) {
@@ -207,47 +204,14 @@ __global__ __launch_bounds__(64) void k_shift_close(ShiftScalars *ss, const doub
     ss->res_prev[lane] = ss->res_last[lane];
 }
 
-// Per shift j (one workgroup each): ||Y_j + sigma_j x_j - b||^2, ||b||^2, ||x_j||^2 in a fixed order; Y_j = A x_j.
-__global__ __launch_bounds__(1024) void k_shift_norms(int n, long lda, const double *__restrict__ Y, const double *__restrict__ b,
-                                                      const double *__restrict__ X, ShiftScalars *ss)
-{
-    __shared__ double lds[3][16];
-    const int j = blockIdx.x;
-    const double sig = ss->sigma[j];
-    double e = 0.0, bb = 0.0, xx = 0.0;
-    for (long i = threadIdx.x; i < n; i += 1024) {
-        const long off = (long)j * lda + i;
-        const double bi = b[i], xi = X[off], d = fma(sig, xi, Y[off]) - bi;
-        e += d * d;
-        bb += bi * bi;
-        xx += xi * xi;
-    }
-    e = wave_sum(e);
-    bb = wave_sum(bb);
-    xx = wave_sum(xx);
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    if (lane == 0) {
-        lds[0][w] = e;
-        lds[1][w] = bb;
-        lds[2][w] = xx;
-    }
-    __syncthreads();
-    if (threadIdx.x < 3) {
-        double s = lds[threadIdx.x][0];
-        for (int t = 1; t < 16; ++t) s += lds[threadIdx.x][t];
-        ss->norms[j][threadIdx.x] = s;
-    }
-}
-
 }  // namespace
 
 hipError_t launch_shift_begin(int n, long lda, int nshift, const double *sigma, const double *b, double *X, double *P, ShiftScalars *ss,
                               hipStream_t s)
 {
     if (nshift < 1 || nshift > kMaxShifts || n < 1 || lda < n) return hipErrorInvalidValue;
-    ShiftSigmas sg{};
-    for (int j = 0; j < nshift; ++j) sg.v[j] = sigma[j];
-    hipLaunchKernelGGL(k_shift_begin, dim3(update_xr_grid((int)lda)), dim3(256), 0, s, n, lda, nshift, sg, b, X, P, ss);
+    hipLaunchKernelGGL(k_shift_begin, dim3(update_xr_grid((int)lda)), dim3(256), 0, s, n, lda, nshift, column_sigmas(sigma, nshift), b, X,
+                       P, ss);
     return hipGetLastError();
 }
 
@@ -263,14 +227,6 @@ hipError_t launch_shift_close(ShiftScalars *ss, const double *rrp, int nrr, int 
 {
     if (nshift < 1 || nshift > kMaxShifts || nrr < 1 || k < 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_shift_close, dim3(1), dim3(64), 0, s, ss, rrp, nrr, nshift, k);
-    return hipGetLastError();
-}
-
-hipError_t launch_shift_norms(int n, long lda, int nshift, const double *Y, const double *b, const double *X, ShiftScalars *ss,
-                              hipStream_t s)
-{
-    if (nshift < 1 || nshift > kMaxShifts || n < 1 || lda < n) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(k_shift_norms, dim3(nshift), dim3(1024), 0, s, n, lda, Y, b, X, ss);
     return hipGetLastError();
 }
 

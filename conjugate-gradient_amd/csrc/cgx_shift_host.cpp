@@ -7,12 +7,6 @@
 // shift scalars live in ONE device allocation of the context (cgx_ctx::shift), made on first use and freed with the problem.
 #include "cgx_internal.h"
 
-#include <algorithm>
-#include <cmath>
-#include <cstring>
-#include <string>
-#include <vector>
-
 using namespace cgxi;
 
 namespace {
@@ -47,57 +41,15 @@ cgx_status ensure_shift(cgx_ctx *ctx, ShiftView *v)
     return CGX_OK;
 }
 
-// The checks in the order check_multi (cgx_multi_host.cpp) makes them: context, problem, transport and storage, arguments.
-cgx_status check_shifted(cgx_ctx *ctx, int nshift, const double *sigma, const double *X, long ldx)
-{
-    const std::string fn("cgx_solve_shifted");
-    CGX_TRY(check_one_gpu_call(ctx, fn));
-    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense or CSR storage only (not CGX_MATRIX_BANDED)");
-    if (ctx->precond != CGX_PRECOND_NONE)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": no preconditioner (it breaks the collinearity of the shifted residuals; "
-                                                   "cgx_set_preconditioner)");
-    if (ctx->res_forced)
-        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": the persistent kernels (gemv_variant 40000 / 50000) have no shifted form");
-    if (nshift < 1 || nshift > CGX_MAX_SHIFTS) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nshift must be 1 .. CGX_MAX_SHIFTS");
-    if (!sigma || !X) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
-    if (ldx < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");
-    for (int j = 0; j < nshift; ++j)
-        if (!(sigma[j] >= 0.0) || !std::isfinite(sigma[j]))
-            return fail(ctx, CGX_ERR_BAD_ARG, fn + ": shift " + std::to_string(j) + " is negative or not finite");
-    if (!ctx->have_b) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no source term set");
-    return CGX_OK;
-}
-
 }  // namespace
-
-// The true residuals of nshift shifted systems, enqueued: Y_j = A x_j (dense: one pass over A for all shifts; CSR: one SpMV per
-// shift), then ss->norms[j] = ||Y_j + ss->sigma[j] x_j - b||^2, ||b||^2, ||x_j||^2.
-cgx_status cgxi::shifted_residual_norms(cgx_ctx *ctx, int nshift, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
-                                        cgx::ShiftScalars *ss)
-{
-    Shard &s = ctx->shards[0];
-    hipStream_t st = ctx->stream;
-    const long lda = ctx->lda;
-    if (ctx->csr) {
-        for (int j = 0; j < nshift; ++j)
-            HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, lda, X + (size_t)j * lda, Y + (size_t)j * lda,
-                                                    s.k1_part(), st));
-    } else {
-        // always the full width kS: a row's sum order depends on the kernel width, and a shift's result must not depend on how many
-        // others there are (the columns beyond nshift hold zeros or an earlier call's x)
-        cgx::MultiArgs g = plain_k1m_args(ctx, kS, X, Y, k1p);
-        g.ms = ms;
-        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
-    }
-    HIP_TRY(ctx, cgx::launch_shift_norms(ctx->n, lda, nshift, Y, s.b_full, X, ss, st));
-    return CGX_OK;
-}
 
 extern "C" {
 
 cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, double *X, long ldx, cgx_result *res)
 {
-    CGX_TRY(check_shifted(ctx, nshift, sigma, X, ldx));
+    CGX_TRY(check_shift_call(ctx, "cgx_solve_shifted", "CGX_MAX_SHIFTS", false,
+                             "no preconditioner (it breaks the collinearity of the shifted residuals; cgx_set_preconditioner)", "shifted",
+                             nshift, sigma, X, ldx));
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     ShiftView v;
     CGX_TRY(ensure_shift(ctx, &v));
@@ -152,32 +104,19 @@ cgx_status cgx_solve_shifted(cgx_ctx *ctx, int nshift, const double *sigma, doub
     HIP_TRY(ctx, hipStreamSynchronize(st));
     const double t_loop = wall_now() - t0;
 
-    CGX_TRY(shifted_residual_norms(ctx, nshift, v.X, v.Y, v.k1p, v.ms, v.ss));
+    // always the full width kS: a row's sum order depends on the kernel width, and a shift's result must not depend on how many
+    // others there are (the columns beyond nshift hold zeros or an earlier call's x)
+    CGX_TRY(column_residual_norms(ctx, nshift, kS, v.X, v.Y, v.k1p, v.ms, s.b_full, 0, sigma, &v.ss->norms[0][0]));
     cgx::ShiftScalars hs;
     HIP_TRY(ctx, hipMemcpyAsync(&hs, v.ss, sizeof hs, hipMemcpyDeviceToHost, st));
     CGX_TRY(download_columns(ctx, X, ldx, v.X, nshift));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (ctx->ev_used || ctx->upd_used || ctx->steps_ev_pending) CGX_TRY(harvest_gemv_events(ctx));
 
-    if (res) {
-        cgx_result base;
-        memset(&base, 0, sizeof base);
-        base.seconds_solve = wall_now() - t_begin;
-        base.seconds_loop = t_loop;
-        fill_k1_stats(ctx, &base);
-        base.gemv_bytes = one_gpu_gemv_bytes(ctx);
-        for (int j = 0; j < nshift; ++j) {
-            cgx_result &o = res[j];
-            o = base;
-            const bool frozen = hs.frozen_at[j] != cgx::kShiftLive;
-            o.iterations = frozen ? hs.frozen_at[j] : k;
-            o.converged = frozen ? 1 : 0;
-            o.residual_prev = hs.res_prev[j];
-            o.residual_last = hs.res_last[j];
-            o.x_norm = std::sqrt(hs.norms[j][2]);
-            o.rel_residual = std::sqrt(hs.norms[j][0]) / std::sqrt(hs.norms[j][1]);
-        }
-    }
+    fill_column_results(ctx, res, nshift, t_begin, t_loop, one_gpu_gemv_bytes(ctx), true, hs.norms, [&](int j) {
+        const bool frozen = hs.frozen_at[j] != cgx::kShiftLive;
+        return ColumnOutcome{frozen ? hs.frozen_at[j] : k, frozen ? 1 : 0, hs.res_prev[j], hs.res_last[j]};
+    });
     return CGX_OK;
 }
 

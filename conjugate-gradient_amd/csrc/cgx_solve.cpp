@@ -556,6 +556,48 @@ void fill_k1_stats(const cgx_ctx *ctx, cgx_result *res)
     }
 }
 
+void fill_column_results(const cgx_ctx *ctx, cgx_result *res, int ncol, double t_begin, double t_loop, double gemv_bytes, bool k1_stats,
+                         const double (*norms)[3], const std::function<ColumnOutcome(int)> &outcome)
+{
+    if (!res) return;
+    cgx_result base;
+    memset(&base, 0, sizeof base);
+    base.seconds_solve = wall_now() - t_begin;
+    base.seconds_loop = t_loop;
+    if (k1_stats) fill_k1_stats(ctx, &base);
+    base.gemv_bytes = gemv_bytes;
+    for (int j = 0; j < ncol; ++j) {
+        cgx_result &o = res[j];
+        o = base;
+        const ColumnOutcome c = outcome(j);
+        o.iterations = c.iterations;
+        o.converged = c.converged;
+        o.residual_prev = c.residual_prev;
+        o.residual_last = c.residual_last;
+        o.x_norm = std::sqrt(norms[j][2]);
+        o.rel_residual = std::sqrt(norms[j][0]) / std::sqrt(norms[j][1]);
+    }
+}
+
+cgx_status column_residual_norms(cgx_ctx *ctx, int ncol, int width, const double *X, double *Y, double *k1p, cgx::MultiScalars *ms,
+                                 const double *b, long ldb, const double *sigma, double *norms)
+{
+    Shard &s = ctx->shards[0];
+    hipStream_t st = ctx->stream;
+    const long lda = ctx->lda;
+    if (ctx->csr) {
+        for (int j = 0; j < ncol; ++j)
+            HIP_TRY(ctx, cgx::launch_spmv_csr_plain(s.plan, s.csr, s.rows, s.row0, lda, X + (size_t)j * lda, Y + (size_t)j * lda,
+                                                    s.k1_part(), st));
+    } else {
+        cgx::MultiArgs g = plain_k1m_args(ctx, width, X, Y, k1p);
+        g.ms = ms;
+        HIP_TRY(ctx, cgx::launch_multi_gemv(g, false, st));
+    }
+    HIP_TRY(ctx, cgx::launch_column_norms(ctx->n, lda, ncol, Y, X, b, ldb, sigma, norms, st));
+    return CGX_OK;
+}
+
 // CSR: values, columns, row pointers, Ap written and p read once (the dense definition's counterpart)
 double one_gpu_gemv_bytes(const cgx_ctx *ctx)
 {
@@ -579,6 +621,25 @@ cgx_status check_dense_one_gpu(cgx_ctx *ctx, const std::string &fn)
 {
     CGX_TRY(check_one_gpu_call(ctx, fn));
     if (ctx->sparse()) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense storage only (CGX_MATRIX_DENSE)");
+    return CGX_OK;
+}
+
+cgx_status check_shift_call(cgx_ctx *ctx, const char *name, const char *limit, bool negative_ok, const char *precond, const char *form,
+                            int nshift, const double *sigma, const double *X, long ldx)
+{
+    const std::string fn(name);
+    CGX_TRY(check_one_gpu_call(ctx, fn));
+    if (ctx->banded) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": dense or CSR storage only (not CGX_MATRIX_BANDED)");
+    if (ctx->precond != CGX_PRECOND_NONE) return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": " + precond);
+    if (ctx->res_forced)
+        return fail(ctx, CGX_ERR_UNSUPPORTED, fn + ": the persistent kernels (gemv_variant 40000 / 50000) have no " + form + " form");
+    if (nshift < 1 || nshift > cgx::kMaxRhs) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": nshift must be 1 .. " + limit);
+    if (!sigma || !X) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": null pointer");
+    if (ldx < ctx->n) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": leading dimension smaller than n");
+    for (int j = 0; j < nshift; ++j)
+        if (!std::isfinite(sigma[j]) || (!negative_ok && !(sigma[j] >= 0.0)))
+            return fail(ctx, CGX_ERR_BAD_ARG, fn + ": shift " + std::to_string(j) + (negative_ok ? " is not finite" : " is negative or not finite"));
+    if (!ctx->have_b) return fail(ctx, CGX_ERR_BAD_ARG, fn + ": no source term set");
     return CGX_OK;
 }
 

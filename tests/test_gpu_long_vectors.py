@@ -23,7 +23,7 @@ d. test_block_inverses_of_the_second_trip    W itself for every row from 262144 
                                              k_bj_invert on the blocks past 262144 and on the truncated one)
 e. test_zero_shift_is_the_plain_solve        fold_pap_strided in k_shift_update against k_update_xr_strided, rr_finish's loop over the
                                              partials from 256 on against head_finish's, pap_strided set by the host
-f. test_every_shift_against_longdouble       k_shift_update<8>'s second loop (it reads P and X again), k_shift_norms and the
+f. test_every_shift_against_longdouble       k_shift_update<8>'s second loop (it reads P and X again), k_column_norms<true> and the
                                              |zeta| sqrt(r.r) stores: every reported number against a value computed outside
 g. test_widths_and_companions                k_shift_update<1>, <8> and <16> in the second loop, masked shifts
 h. test_a_frozen_shift_stays_frozen_in_the_second_trip   the skip on s_flag in the second loop, rows below and from 262144 on

@@ -92,7 +92,7 @@ def test_fixed_iterations_against_oracle(gpu_pkg, oracle, kind, n, storage, vari
 
 @pytest.mark.parametrize("storage", ["dense", "csr"])
 def test_reported_numbers_against_oracle(gpu_pkg, oracle, storage):
-    """What a shift reports, against values computed outside the library (for sigma != 0 they come from k_shift_norms and the
+    """What a shift reports, against values computed outside the library (for sigma != 0 they come from k_column_norms and the
     |zeta| sqrt(r.r) stores alone): residual_prev and residual_last against the oracle's on the shifted matrix, 1e-9 relative
     (the bar of tests/test_gpu_parity.py test_full_size_properties for reported residuals); x_norm against ||x||, 1e-12;
     rel_residual against ||(A + sigma I) x - b|| / ||b|| recomputed on the host from the returned x, 1e-9 relative plus the
